@@ -3,13 +3,17 @@
 cost + gradient w.r.t. all distributed parameters and initial states) on a synthetic catchment with
 hourly x 1 yr forcing resident in HBM (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
-A "step" is one forward+adjoint sweep of the hot path over the whole (grid x nt) batch.
+A "step" is one forward+adjoint sweep of the hot path over the whole (grid x nt) batch.  A plain run sets up, runs W untimed and
+K timed steps and prints the line (value, ms_per_step, roofline of the dominant kernel, per-kernel times of the timed steps);
+--dump-outputs DIR also writes what the last timed step computed (dump_outputs).  --full attaches everything that takes runs of
+its own, listed below.
   N = 1   the largest single-GPU configuration of BASELINE.json: the 2048 x 2048 grid of configs[3], 8760 steps, gr-b, compact
-          forcing resident, adjoint checkpointed in storage chunks.  The same line carries "secondary" (configs[2]: 1024 x 1024,
-          store-all adjoint), "tile_solo" (the 2048 x 1024 tile one GPU owns in the 8-GPU decomposition of configs[4], alone:
-          the like-for-like base of the N > 1 lines), "exact_libm" (the bit-exact build) and "cpu_baseline".
+          forcing resident, adjoint checkpointed in storage chunks.  With --full the same line carries "secondary" (configs[2]:
+          1024 x 1024, store-all adjoint), "tile_solo" (the 2048 x 1024 tile one GPU owns in the 8-GPU decomposition of configs[4],
+          alone: the like-for-like base of the N > 1 lines), "real_d8", "forward_only" (configs[1]), "exact_libm" (the bit-exact
+          build), "inclusive_ms_per_step" and "cpu_baseline".
   N > 1   one process per GPU, every GPU owns a 2048 x 1024 tile: 1x2, 2x2, 2x4 tiles = 2048x2048, 4096x2048 and, at
           N = 8, the 4096 x 4096 grid the metric is quoted on (configs[4]).  Boundary discharge series move between the
           tiles with grouped ncclSend / ncclRecv posted by the library itself on its routing stream (RCCL over xGMI);
@@ -17,6 +21,7 @@ A "step" is one forward+adjoint sweep of the hot path over the whole (grid x nt)
           Under a launcher (torchrun: RANK / WORLD_SIZE in the environment) the process is one rank; without one,
           --gpus N starts the N ranks itself as fresh child processes before anything here touches the GPU.
           --tile-rows / --tile-cols (or --grid) choose another per-GPU tile, e.g. --grid 1024 for the 1024^2-per-GPU series.
+          With --full, rank 0's tile is timed once more alone after the timed region ("tile_solo", "efficiency_vs_solo_tile").
 Prints ONE JSON line on rank 0.
 
 PyTorch is plumbing here (device memory for building the forcing in HBM, streams, torch.distributed);
@@ -107,11 +112,17 @@ def parse(argv=None):
     ap.add_argument("--cpu-cores", type=int, default=0, help="replicas of the CPU baseline (default: the box's CPU share, at most 16)")
     ap.add_argument("--cpu-solo-grid", type=int, default=512, help="the one-replica CPU measurement: grid (its tape leaves every cache level)")
     ap.add_argument("--cpu-solo-nt", type=int, default=160)
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own (CPU baseline, inclusive call, the "
+                    "attached workloads, the exact-libm build; N > 1: rank 0's tile alone); the --no-* options above then drop parts of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed as "
+                    "DIR/<name>.npy (float32 / float64, a fixed sample of cells of planes larger than DUMP_SAMPLE_CELLS)")
     a = ap.parse_args(argv)
-    if a.profile:
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.profile or not a.full:
         a.no_secondary = a.no_tile_solo = a.no_exact = a.no_cpu_baseline = a.no_inclusive = a.no_forward_only = a.no_real_d8 = True
-        if a.gpus != 1:
-            ap.error("--profile is a single-process run")
+    if a.profile and a.gpus != 1:
+        ap.error("--profile is a single-process run")
     return a
 
 
@@ -225,6 +236,42 @@ def chunk_plan(nt, cells, hbm_bytes, forcing_bytes, structure, forced=0):
     return min(tc, ((nt + nch - 1) // nch + 15) // 16 * 16)
 
 
+def forcing_block(rows, cols, t0, t1, device):
+    """synth.forcing_block(rows, cols, t0, t1, xp=torch, device=device), bit for bit, in a fifth of the device time (the 2048^2 x 8760
+    forcing of the headline: ~5 s against ~22 s, most of the set-up of a plain run): the storm
+    field of synth.prcp_counts depends on the step only through its storm time block (t // _TB) and on the cell only through its
+    _BS x _BS block and the offsets in it, so its four lattice nodes are hashed once per (time block, lattice point) and gathered,
+    and the interpolated depth is formed once per time block.  The hourly modulation (per step) and the gap hash (per step and
+    cell) are synth's own expressions.  Integer arithmetic throughout, then synth's float32 multiply: the same values on any device
+    (tests/test_bench_cpu.py holds the two generators equal)."""
+    import torch
+    from smash_amd import synth
+    bs, tb, seed = synth._BS, synth._TB, synth.SEED
+    r, c = rows.to(torch.int64)[None, :], cols.to(torch.int64)[None, :]
+    t = torch.arange(t0, t1, dtype=torch.int64, device=device)[:, None]
+    R, x, C, y = r // bs, r % bs, c // bs, c % bs
+    nr, nc = int(R.max()) + 2, int(C.max()) + 2                              # lattice points R .. R + 1, C .. C + 1
+    T = torch.arange(t0 // tb, (t1 - 1) // tb + 1, dtype=torch.int64, device=device)
+    h = synth._hash3(seed, T[:, None, None] * 4099 + 1, torch.arange(nr, dtype=torch.int64, device=device)[None, :, None],
+                     torch.arange(nc, dtype=torch.int64, device=device)[None, None, :])
+    lattice = torch.where((h & 0xFF) < 56, (h >> 8) & 0xFFF, torch.zeros_like(h)).reshape(T.numel(), nr * nc)
+
+    def node(dr, dc):
+        return lattice.index_select(1, ((R + dr) * nc + (C + dc))[0])
+
+    v = (node(0, 0) * (bs - x) * (bs - y) + node(1, 0) * x * (bs - y) + node(0, 1) * (bs - x) * y + node(1, 1) * x * y) >> 12
+    m = synth._hash3(seed + 1, t, 3, 5) & 0xF
+    m = torch.where(m < 8, m * 0, m - 7)
+    n = ((v * v).index_select(0, (t // tb - t0 // tb)[:, 0]) * m) >> 19
+    gap = (synth._hash3(seed + 2, t, r, c) % 1000000) < 1000           # synth's default gap_per_million
+    prcp = n.to(torch.float32) * 0.1
+    prcp = torch.where(gap, torch.full_like(prcp, -99.0), prcp)
+    daily, w = synth._pet_tables()
+    tt = np.arange(t0, t1)
+    pet1 = torch.from_numpy((daily[(tt // 24) % 366] * w[tt % 24]).astype(np.float32)).to(device)
+    return prcp, pet1[:, None].expand(prcp.shape).contiguous()
+
+
 class Case:
     """One benchmark workload: plan + forcing resident in HBM + observations, ready to sweep."""
 
@@ -296,7 +343,7 @@ class Case:
         tb = max(24, (1 << 26) // max(sol.ncells, 1) // 24 * 24)     # whole days; ~64 M cell-steps of int64 temporaries per block
         for t0 in range(0, nt, tb):
             t1 = min(nt, t0 + tb)
-            prcp, pet = synth.forcing_block(d_rows, d_cols, t0, t1, xp=torch, device=dev)
+            prcp, pet = forcing_block(d_rows, d_cols, t0, t1, dev)
             torch.cuda.synchronize()
             sol.set_forcing_device_block(t0, t1, prcp.data_ptr(), pet.data_ptr())
             del prcp, pet
@@ -356,6 +403,40 @@ def timed_sweeps(case, steps, warmup, adjoint, barrier):
     barrier()
     secs = time.perf_counter() - t0
     return secs, {k: v / steps for k, v in tm_acc.items()}
+
+
+# the fields each structure's sweep reads and differentiates: what smashx_download fills (tests/golden_util.py keeps the same lists)
+STRUCT_PARAMS = {"gr-a": ("cp", "cft", "exc", "lr"), "gr-b": ("ci", "cp", "cft", "exc", "lr"),
+                 "gr-c": ("ci", "cp", "cft", "cst", "exc", "lr"), "gr-d": ("cp", "cft", "lr"),
+                 "vic-a": ("b", "cusl1", "cusl2", "clsl", "ks", "ds", "dsm", "ws", "lr")}
+STRUCT_STATES = {"gr-a": ("hp", "hft", "hlr"), "gr-b": ("hi", "hp", "hft", "hlr"),
+                 "gr-c": ("hi", "hp", "hft", "hst", "hlr"), "gr-d": ("hp", "hft", "hlr"),
+                 "vic-a": ("husl1", "husl2", "hlsl", "hlr")}
+DUMP_SAMPLE_CELLS = 1 << 20      # 4 MB per plane: the 13 planes of vic-a stay below 64 MB
+
+
+def dump_outputs(path, structure, adjoint, out, par_b, sta_b, prefix=""):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as <path>/<prefix><name>.npy -- the cost
+    (float64), the discharge at the gauges (ng, nt) and either the gradient of every parameter and initial state the structure
+    uses (adjoint sweep: <name>_b) or its final states (forward sweep: fstates_<name>).  A plane of more than DUMP_SAMPLE_CELLS
+    cells is written as the same seeded sample of its cells (column-major flat indices, ascending) in every run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"cost": np.array([out.cost, out.cost_jobs, out.cost_jreg], np.float64), "qsim": np.asarray(out.qsim, np.float32)}
+    if adjoint:
+        planes = {k + "_b": getattr(par_b, k) for k in STRUCT_PARAMS[structure]}
+        planes.update({k + "_b": getattr(sta_b, k) for k in STRUCT_STATES[structure]})
+    else:
+        planes = {"fstates_" + k: getattr(out.fstates, k) for k in STRUCT_STATES[structure]}
+    idx = None
+    for k, v in planes.items():
+        v = np.asarray(v, np.float32).reshape(-1, order="F")
+        if v.size > DUMP_SAMPLE_CELLS:
+            if idx is None:
+                idx = np.sort(np.random.default_rng(20240501).choice(v.size, DUMP_SAMPLE_CELLS, replace=False))
+            v = v[idx]
+        arrays[k] = v
+    for k, v in arrays.items():
+        np.save(os.path.join(path, prefix + k + ".npy"), v)
 
 
 def inclusive_call_ms(case, adjoint, reps=3):
@@ -519,6 +600,8 @@ def main():
             ct = torch.tensor([cost], dtype=torch.float64, device=cdev)
             dist.all_reduce(ct, op=dist.ReduceOp.SUM)
             cost = float(ct.item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, a.structure, adjoint, case.out, par_b, sta_b, f"rank{rank}_" if world > 1 else "")
     inclusive = inclusive_call_ms(case, adjoint) if world == 1 and not solo and not a.no_inclusive else None
 
     if rank == 0 and a.trace_groups:

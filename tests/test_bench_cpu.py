@@ -59,7 +59,12 @@ def test_default_single_gpu_workload_is_the_largest_configuration():
     import bench
     a = bench.parse([])
     assert a.gpus == 1 and a.grid == 0 and a.secondary_grid == 1024 and a.mesh == "synth"
-    assert not (a.no_forward_only or a.no_real_d8 or a.no_exact)          # the line carries configs[1], the real river network, the exact build
+    # a plain run measures the headline only
+    assert a.no_secondary and a.no_tile_solo and a.no_exact and a.no_cpu_baseline and a.no_inclusive and a.no_forward_only and a.no_real_d8
+    f = bench.parse(["--full"])
+    assert f.gpus == 1 and f.grid == 0 and f.secondary_grid == 1024 and f.mesh == "synth"
+    assert not (f.no_forward_only or f.no_real_d8 or f.no_exact)          # the line carries configs[1], the real river network, the exact build
+    assert not (f.no_secondary or f.no_tile_solo or f.no_cpu_baseline or f.no_inclusive)
     p = bench.parse(["--profile"])
     assert p.no_secondary and p.no_tile_solo and p.no_exact and p.no_cpu_baseline and p.no_inclusive and p.no_forward_only and p.no_real_d8
 
@@ -132,3 +137,52 @@ def test_pmc_summary_divides_every_family_by_the_cell_steps_it_swept(tmp_path):
     assert d["sx_k_chain_transpose_gather"]["hbm_bytes_per_cellstep_corrected"] == pytest.approx(per(1.0, 2.0, 4000.0))
     assert d["sx_k_chain_transpose_scatter"]["hbm_bytes_per_cellstep_corrected"] == pytest.approx(per(2.0, 4.0, 2000.0))
     assert d["sx_k_vert_fwd"]["dispatches"] == 2 and d["workload"]["forward_only"] is False
+
+
+def test_bench_forcing_generator_is_synths_bit_for_bit():
+    """bench.forcing_block (storm field hashed once per time block and lattice point) writes exactly the forcing of
+    synth.forcing_block: windows that start on and off a storm time block and a day, cells on and off the lattice lines,
+    gaps included, in the cell order of a plan (not row-major)."""
+    import numpy as np
+    import torch
+    import bench
+    from smash_amd import synth
+    rng = np.random.default_rng(3)
+    rows = rng.permutation(np.repeat(np.arange(200), 3))[:500]
+    cols = rng.integers(0, 300, 500)
+    rows[:4], cols[:4] = (0, 63, 64, 199), (0, 64, 127, 299)
+    d_rows, d_cols = torch.from_numpy(rows.astype(np.int64)), torch.from_numpy(cols.astype(np.int64))
+    for t0, t1 in ((0, 24), (24, 48), (5, 31), (8735, 8760), (3, 4)):
+        p, e = bench.forcing_block(d_rows, d_cols, t0, t1, "cpu")
+        rp, re_ = synth.forcing_block(d_rows, d_cols, t0, t1, xp=torch, device="cpu")
+        np_p, np_e = synth.forcing_block(rows, cols, t0, t1)
+        assert p.dtype == torch.float32 and p.shape == (t1 - t0, rows.size)
+        assert torch.equal(p, rp) and torch.equal(e, re_), (t0, t1)
+        assert np.array_equal(p.numpy(), np_p) and np.array_equal(e.numpy(), np_e), (t0, t1)
+    p, _ = bench.forcing_block(d_rows, d_cols, 0, 2400, "cpu")
+    assert (p == -99.0).any() and (p > 0).any()          # gaps and rain both present
+
+
+def test_dump_outputs_writes_the_callers_arrays_within_64_mb(tmp_path):
+    """--dump-outputs: cost (float64), discharge and the gradient planes of the structure's fields (float32); a 2048^2 plane is
+    written as the same seeded sample of cells in every run, and the widest structure stays below 64 MB."""
+    import types
+    import numpy as np
+    import bench
+    n = 2048
+    plane = np.asfortranarray(np.arange(n * n, dtype=np.float32).reshape(n, n, order="F"))
+    out = types.SimpleNamespace(cost=0.25, cost_jobs=0.25, cost_jreg=0.0, qsim=np.ones((8, 8760), np.float32, order="F"))
+    grads = types.SimpleNamespace(**{k: plane for k in bench.STRUCT_PARAMS["vic-a"] + bench.STRUCT_STATES["vic-a"]})
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "vic-a", True, out, grads, grads)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(["cost.npy", "qsim.npy"] + [k + "_b.npy" for k in bench.STRUCT_PARAMS["vic-a"] + bench.STRUCT_STATES["vic-a"]])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) < 64 << 20
+    for name in names:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), name
+    s = np.load(tmp_path / "a" / "lr_b.npy")
+    assert s.size == bench.DUMP_SAMPLE_CELLS and np.all(np.diff(s) > 0)      # sampled cells: distinct, in ascending order
+    assert np.load(tmp_path / "a" / "cost.npy").dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
