@@ -440,8 +440,9 @@ static void jobs_d(const orc_config* cfg, const int* flwacc, const int* gauge_po
                    const float* wgauge, const float* qsim, const float* qsim_d, float* jobs_out, float* jobs_d_out) {
     const int ng = cfg->ng, nt = cfg->nt, s0 = cfg->optimize_start_step - 1, n = nt - s0;
     const size_t m = (size_t)(n > 0 ? n : 1);
-    float* qo = (float*)malloc(4 * m); float* qs = (float*)malloc(4 * m); float* qsd = (float*)malloc(4 * m);
-    float* arr = (float*)malloc(4 * (size_t)(ng + 1)); float* arr_d = (float*)malloc(4 * (size_t)(ng + 1));
+    /* sizeof(float), not 4: liboracle64.so compiles these statements with float = double */
+    float* qo = (float*)malloc(sizeof(float) * m); float* qs = (float*)malloc(sizeof(float) * m); float* qsd = (float*)malloc(sizeof(float) * m);
+    float* arr = (float*)malloc(sizeof(float) * (size_t)(ng + 1)); float* arr_d = (float*)malloc(sizeof(float) * (size_t)(ng + 1));
     int arr_size = 0;
     float jobs = 0.f, jd = 0.f;
     for (int g = 0; g < ng; ++g) {

@@ -35,3 +35,15 @@ def test_exact_build_is_bit_identical_on_the_edge_cases():
     sys.stdout.write(r.stdout[-3000:])
     # (five edge cases + the largest basin of the reference's D8 raster of France -- a real river network of 139 742 cells -- on plain and on staging rows)
     assert r.returncode == 0 and "7 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+def test_exact_build_is_bit_identical_at_size():
+    """tests/test_gpu_parity_at_size.py under the exact-libm build: every forward and adjoint output of the wide cases (512^2 with
+    the chained launches on plain and on staging rows, the 957 k cells of France, vic-a and regularised gr-c at 384^2) and of the
+    full-year cases (8760 steps: store-all, compact layout over several storage chunks, cold start, long gaps, a month of warm-up)
+    BIT-IDENTICAL to the oracle; the module skips the fp64 truth there except for the tangent outputs."""
+    env = dict(os.environ, SMASHX_EXACT_LIBM="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity_at_size.py"), "-q", "-m", "gpu",
+                        "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    sys.stdout.write(r.stdout[-6000:])
+    assert r.returncode == 0 and "9 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]

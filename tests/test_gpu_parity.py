@@ -128,17 +128,37 @@ def test_chunking_and_grouping_do_not_change_results(name, chunk, pipe, group):
         assert np.array_equal(getattr(ref[4], k), getattr(alt[4], k)), k
 
 
-@pytest.mark.parametrize("name,chunk,pipe,group", [("gr_c_32x32x240_d8_ragged", 96, 16, 64), ("gr_b_64x64x720_nse", 240, 48, 128), ("vic_a_24x24x240_d8_kge", 64, 32, 64),
-                                                   ("gr_b_20x20x96_d8", 0, 0, 64), ("gr_b_64x64x720_nse", 0, 0, 512)])
-def test_staging_rows_of_the_chained_groups_equal_the_plain_rows(name, chunk, pipe, group, monkeypatch):
+def _staging_case(name, chunk, pipe, group, staged):
+    """A parameter set of the staging test; its id stays name-chunk-pipe-group (staged is the plan's expected state, not a variant)."""
+    return pytest.param(name, chunk, pipe, group, staged, id=f"{name}-{chunk}-{pipe}-{group}")
+
+
+@pytest.mark.parametrize("name,chunk,pipe,group,staged", [_staging_case("gr_c_32x32x240_d8_ragged", 96, 16, 64, False),
+                                                          _staging_case("gr_b_64x64x720_nse", 240, 48, 128, True),
+                                                          _staging_case("vic_a_24x24x240_d8_kge", 64, 32, 64, False),
+                                                          _staging_case("gr_b_20x20x96_d8", 0, 0, 64, False),
+                                                          _staging_case("gr_b_64x64x720_nse", 0, 0, 512, False)])
+def test_staging_rows_of_the_chained_groups_equal_the_plain_rows(name, chunk, pipe, group, staged, monkeypatch):
     """The chained routing launches read their inputs from -- and, in the reverse sweep, write their results to -- staging rows indexed
     by time block + stage, filled and emptied by the LDS-FIFO transposition passes (sx_k_chain_transpose, sx_kernels.h "Staging rows"):
-    a change of addresses only.  Every output bit-identical with SMASHX_CHAIN_STAGE=0, across storage chunks, sub-chunks and group sizes."""
+    a change of addresses only.  Every output bit-identical with SMASHX_CHAIN_STAGE=0, across storage chunks, sub-chunks and group sizes.
+    staged: the plan really runs on staging rows (chain_staged); the others have two routing rounds only, so no round is chained
+    (chain_first needs two rounds after the first) and there is nothing to stage -- asserted, so that no case passes vacuously."""
     g = gu.load(name)
     monkeypatch.setenv("SMASHX_CHAIN_STAGE", "0")
     ref = _run_adjoint(g, chunk_steps=chunk, pipe_steps=pipe, group_size=group)
     monkeypatch.setenv("SMASHX_CHAIN_STAGE", "1")
-    alt = _run_adjoint(g, chunk_steps=chunk, pipe_steps=pipe, group_size=group)
+    import smash_amd
+    setup, mesh, inp, par, sta, out = _types(g, chunk_steps=chunk, pipe_steps=pipe, group_size=group)
+    par_b, sta_b = par.copy(), sta.copy()
+    smash_amd.forward_b(setup, mesh, inp, par, par_b, inp._bgd[0], par.copy(), sta, sta_b, inp._bgd[1], sta.copy(), out,
+                        out.copy(), np.float32(0), np.float32(1))
+    alt = (par, sta, out, par_b, sta_b)
+    tm = inp._smashx_solver.timing()
+    if staged:
+        assert tm["n_chained_groups"] > 0 and tm["chain_staged"] == 1, tm
+    else:
+        assert tm["n_chained_groups"] == 0 and tm["chain_staged"] == 0, tm
     assert np.array_equal(ref[2].qsim, alt[2].qsim) and ref[2].cost == alt[2].cost
     for k in gu.STRUCT_PARAMS[g.structure]:
         assert np.array_equal(getattr(ref[3], k), getattr(alt[3], k)), k
@@ -482,7 +502,7 @@ def test_edge_cases_vs_oracle(case):
     _compare_with_oracle(g)
 
 
-def _compare_with_oracle(g, bar=2e-5):
+def _compare_with_oracle(g, bar=2e-5, plan=False):
     """Forward and adjoint of case g against the plain-C oracle (bit-identical to the reference): default build within `bar`; under the
     exact-libm build (tests/test_gpu_exact.py runs these tests with SMASHX_EXACT_LIBM=1) BIT-IDENTICAL -- cases without a golden vector
     have no reference noise to set a bar by, but the exact build must reproduce the oracle to the last bit: discharge, cost, final
@@ -493,7 +513,16 @@ def _compare_with_oracle(g, bar=2e-5):
     fo = pyoracle.run(st, m, g.dt, g.prcp, g.pet, g.qobs, g.params, g.states)
     bo = pyoracle.run(st, m, g.dt, g.prcp, g.pet, g.qobs, g.params, g.states, adjoint=True)
     par, sta, out = _run_forward(g)
-    par, sta, out2, par_b, sta_b = _run_adjoint(g)
+    if plan:            # the adjoint through a Solver of its own, whose plan is returned (smashx_get_timing)
+        import smash_amd
+        setup, mesh, inp, par, sta, out2 = _types(g, chunk_steps=0)
+        par_b, sta_b = par.copy(), sta.copy()
+        smash_amd.forward_b(setup, mesh, inp, par, par_b, inp._bgd[0], par.copy(), sta, sta_b, inp._bgd[1], sta.copy(), out2,
+                            out2.copy(), np.float32(0), np.float32(1))
+        tm = inp._smashx_solver.timing()
+    else:
+        par, sta, out2, par_b, sta_b = _run_adjoint(g)
+        tm = None
     if _lib.EXACT:
         bad = []
         if m.ng:
@@ -503,7 +532,7 @@ def _compare_with_oracle(g, bar=2e-5):
         bad += [k + "_b" for k in gu.STRUCT_PARAMS[st] if not np.array_equal(getattr(par_b, k), bo["parameters_b"][k])]
         bad += [k + "_b" for k in gu.STRUCT_STATES[st] if not np.array_equal(getattr(sta_b, k), bo["states_b"][k])]
         assert not bad, bad
-        return
+        return tm
     if m.ng:
         assert gu.rel_l2(out.qsim, fo["qsim"]) <= 2e-6 and abs(out.cost - fo["cost"]) <= 1e-5 * abs(fo["cost"]) + 3e-7
     else:
@@ -514,6 +543,7 @@ def _compare_with_oracle(g, bar=2e-5):
         assert gu.rel_l2(getattr(par_b, k), bo["parameters_b"][k]) <= bar, k
     for k in gu.STRUCT_STATES[st]:
         assert gu.rel_l2(getattr(sta_b, k), bo["states_b"][k]) <= bar, k
+    return tm
 
 
 @pytest.mark.parametrize("staged", [False, True])
@@ -530,7 +560,8 @@ def test_real_river_network_vs_oracle(staged, monkeypatch):
     qobs = np.asfortranarray(np.abs(np.random.default_rng(5).standard_normal((m.ng, nt))).astype(np.float32) + 0.1)
     g = type("G", (), {})()
     g.structure, g.dt, g.nt, g.mesh, g.prcp, g.pet, g.qobs, g.params, g.states, g.opts = "gr-b", 3600.0, nt, m, prcp, pet, qobs, P, S, {}
-    _compare_with_oracle(g)
+    tm = _compare_with_oracle(g, plan=True)
+    assert tm["n_chained_groups"] > 0 and tm["chain_staged"] == int(staged), tm       # the staged case really runs on staging rows
 
 
 def test_error_behaviour():
