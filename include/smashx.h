@@ -355,6 +355,34 @@ int smashx_selftest_math(int device, long long n, unsigned seed, float blo, floa
  * Both must be 0: the paths execute the same operations. */
 int smashx_selftest_paths(int device, long long n, unsigned seed, long long* out);
 
+/* Device evaluator of the math layer (sx_math.h, and sx_libm.h in the exact-libm build): out0[i] (and out1[i] for the paired ids) =
+ * entry `fn` applied to x[i] (and y[i]), n <= 2^26 elements per call, one elementwise kernel that stages the exact build's tables
+ * first (SX_LIBM_INIT) as the sweep kernels do.  Element i is evaluated by lane i % 64 of a wavefront (SMASHX_FN_DIV4: the four
+ * elements 4i .. 4i+3, divided by y[4i], by lane i % 64; n a multiple of 4), so the caller decides which arguments share a
+ * wavefront: uniform ones take the wave-uniform shortcuts, one odd lane forces the guarded forms.  tests/test_gpu_math.py compares
+ * every id with glibc, with a correctly rounded value and with the host build of the same headers. */
+enum {
+    SMASHX_FN_TANH = 0,            /* sx_tanhf(x)                                   */
+    SMASHX_FN_TANH_BRANCHY = 1,    /* sx_tanhf(x, false): the branchy restatement   */
+    SMASHX_FN_EXPM1 = 2,           /* sx_expm1f(x)                                  */
+    SMASHX_FN_EXP = 3,             /* sx_expf(x)                                    */
+    SMASHX_FN_LOG = 4,             /* sx_logf(x)                                    */
+    SMASHX_FN_POW = 5,             /* sx_powf(x, y)                                 */
+    SMASHX_FN_POWB = 6,            /* sx_powb(sx_powbase(x), y) -> out0, sx_logb -> out1 */
+    SMASHX_FN_POW_M4 = 7,          /* x^-4                                          */
+    SMASHX_FN_POW_M4_M5 = 8,       /* x^-4 -> out0, x^-5 -> out1                    */
+    SMASHX_FN_POW_M025 = 9,        /* x^-1/4                                        */
+    SMASHX_FN_POW_M025_M125 = 10,  /* x^-1/4 -> out0, x^-5/4 -> out1                */
+    SMASHX_FN_POW_3P5 = 11,        /* x^3.5                                         */
+    SMASHX_FN_POW_3P5_2P5 = 12,    /* x^3.5 -> out0, x^2.5 -> out1                  */
+    SMASHX_FN_DIV = 13,            /* sx_div(x, sx_mkdiv(y))                        */
+    SMASHX_FN_DIV4 = 14,           /* sx_div4: x[4i .. 4i+3] / y[4i]                */
+    SMASHX_FN_FDIV = 15,           /* sx_fdiv(x, y)                                 */
+    SMASHX_FN_DIV_FAST = 16,       /* sx_div(x, sx_mkdiv_fast(y))                   */
+    SMASHX_FN_COUNT = 17
+};
+int smashx_selftest_eval(int device, int fn, const float* x, const float* y, long long n, float* out0, float* out1);
+
 /* ---- L-BFGS-B, the optimiser of the variational calibration (reference: lbfgsb.f driven by optimize_lbfgsb,
  * smash/solver/optimize/mw_optimize.f90:484-676: m = 10, factr, pgtol, bounds of the normalised control, reverse communication).
  * A from-the-paper implementation (Byrd-Lu-Nocedal-Zhu 1995, Morales-Nocedal 2011, More'-Thuente line search; smash_amd/csrc/

@@ -18,6 +18,7 @@
 #include "sx_jreg.h"
 #include "sx_kernels.h"
 #include "sx_plan.h"
+#include "sx_selftest.h"
 
 namespace {
 
@@ -247,6 +248,14 @@ __global__ void k_selftest_paths(unsigned long long n, unsigned seed, unsigned l
     }
     if (bad_t) atomicAdd(out, bad_t);
     if (bad_p) atomicAdd(out + 1, bad_p);
+}
+
+// elementwise evaluator of the math layer (smashx_selftest_eval): thread t evaluates element t (SMASHX_FN_DIV4: elements 4t .. 4t+3),
+// so element i sits on lane i % 64 (blockDim and the grid stride are multiples of 64)
+__global__ void k_selftest_eval(int fn, const float* x, const float* y, long long nt, float* o0, float* o1) {
+    SX_LIBM_INIT();      // exact-libm build: the tables into LDS, as in the sweep kernels
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < nt; t += (long long)gridDim.x * blockDim.x)
+        sx_selftest_eval1(fn, x, y, t, o0, o1);
 }
 
 // whole-domain outputs: T4 chunk buffer -> planes of `plane` floats per time step, cell k at idx[k]
@@ -1790,6 +1799,35 @@ int smashx_selftest_paths(int device, long long n, unsigned seed, long long* out
     (void)hipFree(d);
     if (e != hipSuccess) return fail(SMASHX_E_HIP, hipGetErrorString(e));
     out[0] = (long long)h[0]; out[1] = (long long)h[1];
+    return 0;
+}
+
+int smashx_selftest_eval(int device, int fn, const float* x, const float* y, long long n, float* out0, float* out1) {
+    const bool binary = fn == SMASHX_FN_POW || fn == SMASHX_FN_POWB || fn == SMASHX_FN_DIV || fn == SMASHX_FN_DIV4 ||
+                        fn == SMASHX_FN_FDIV || fn == SMASHX_FN_DIV_FAST;
+    const bool paired = fn == SMASHX_FN_POWB || fn == SMASHX_FN_POW_M4_M5 || fn == SMASHX_FN_POW_M025_M125 || fn == SMASHX_FN_POW_3P5_2P5;
+    if (fn < 0 || fn >= SMASHX_FN_COUNT) return fail(SMASHX_E_ARG, "unknown math function id");
+    if (!x || !out0 || (binary && !y) || (paired && !out1)) return fail(SMASHX_E_ARG, "null argument");
+    if (n <= 0 || n > (1ll << 26) || (fn == SMASHX_FN_DIV4 && n % 4 != 0)) return fail(SMASHX_E_ARG, "n must be in [1, 2^26] (DIV4: a multiple of 4)");
+    if (device >= 0) HIPCHK(hipSetDevice(device));
+    const size_t b = (size_t)n * sizeof(float);
+    float *dx = nullptr, *dy = nullptr, *d0 = nullptr, *d1 = nullptr;
+    hipError_t e = hipMalloc((void**)&dx, b);
+    if (e == hipSuccess) e = hipMalloc((void**)&d0, b);
+    if (e == hipSuccess && binary) e = hipMalloc((void**)&dy, b);
+    if (e == hipSuccess && paired) e = hipMalloc((void**)&d1, b);
+    if (e == hipSuccess) e = hipMemcpy(dx, x, b, hipMemcpyHostToDevice);
+    if (e == hipSuccess && binary) e = hipMemcpy(dy, y, b, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const long long nt = fn == SMASHX_FN_DIV4 ? n / 4 : n;
+        const unsigned grid = (unsigned)std::min<long long>((nt + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_selftest_eval, dim3(grid), dim3(256), 0, 0, fn, dx, dy, nt, d0, d1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out0, d0, b, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && paired) e = hipMemcpy(out1, d1, b, hipMemcpyDeviceToHost);
+    (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(d0); (void)hipFree(d1);
+    if (e != hipSuccess) return fail(SMASHX_E_HIP, hipGetErrorString(e));
     return 0;
 }
 

@@ -10,14 +10,16 @@
 //   * glibc 2.35 tanhf is the fdlibm float algorithm (expm1f based) and is NOT correctly rounded
 //     (36 % of results differ from the correctly rounded value), so sx_tanhf restates that published
 //     fdlibm algorithm operation by operation; it is bit-identical to glibc on every float in
-//     [2^-63, 24] (checked exhaustively on the host build of this header, tests/test_sx_math.py).
+//     [2^-63, 24] (checked exhaustively on the host build of this header, tests/test_sx_math.py, and on the device build over
+//     +-[2^-63, 24), tests/test_gpu_math.py).
 // Everything is compiled with -ffp-contract=off; the only fused operations are the explicit fma().
 #pragma once
 
 #include <stdint.h>
 
 // SX_EXACT_LIBM=1 (the libsmashx_exact.so build): every power, exponential and logarithm goes through glibc 2.35's own float
-// algorithms restated in sx_libm.h, every division is the IEEE division.  Slower; exists to show that the default build's
+// algorithms restated in sx_libm.h, every division gives the IEEE quotient (the reciprocal + 2 FMA form only where it provably equals
+// it: sx_div below; checked bit for bit over the whole float range on the device, tests/test_gpu_math.py).  Slower; exists to show that the default build's
 // distance from the reference is libm rounding and nothing else (tests/test_gpu_exact.py, DESIGN.md "Numerics").
 #ifndef SX_EXACT_LIBM
 #define SX_EXACT_LIBM 0
@@ -94,33 +96,44 @@ SX_HD float sx_div_scaled(float a, const SxDiv& D, bool* ok) {
     *ok = fabsf(q3) >= 0x1p-126f;
     return q3;
 }
+#if SX_EXACT_LIBM
+// Exact-libm build: the range the three operations are trusted on.  The reciprocal must be a normal number: for |d| > 2^126 (and for
+// subnormal, zero or non-finite d) D.r has lost bits and the correction no longer gives RN(a / d) -- 2 of 2e7 random pairs with d in
+// [2^127, 2^128) came out one ulp off before this test existed (tests/test_sx_math.py).
+SX_HD bool sx_div_rbad(const SxDiv& D) { const float mr = fabsf(D.r); return !(mr >= 0x1p-126f && mr <= 0x1.fffffep127f); }
+#endif
 SX_HD float sx_div(float a, const SxDiv& D) {
     const float q = a * D.r;
     const float e = fmaf(-D.d, q, a);
-    const float q2 = fmaf(e, D.r, q);
+    float q2 = fmaf(e, D.r, q);
 #if SX_EXACT_LIBM
     // The theorem needs the residual to be exact: outside the comfortable exponent range (tiny quotients on their way to the
-    // subnormals -- the fringe of a decaying adjoint field is full of them -- and huge ones) the exact build takes the IEEE division.
+    // subnormals -- the fringe of a decaying adjoint field is full of them -- huge ones, and numerators below 2^-100, whose residual
+    // underflows even when the quotient is ordinary) and for a denominator whose reciprocal is not a normal number the exact build
+    // takes the IEEE division.  A zero numerator keeps q = a * r, the IEEE zero with its sign (the
+    // residual form turns -0 / d into +0).
     // SX_EXACT_DIV: 0 = per-lane branch (round 2), 1 = the test is made for the whole wavefront (scalar branch, the IEEE expansion
     // only runs in wavefronts that hold such a quotient), 2 = as 1, and quotients below 2^-100 whose IEEE result is still a normal
     // number are obtained exactly from the same three operations on a * 2^64 (a power-of-two scaling commutes with the division's
     // single rounding as long as the result stays normal): only subnormal, zero, huge and non-finite results take the expansion.
+    q2 = (a == 0.f) ? q : q2;
     const float m = fabsf(q2);
+    const bool rbad = sx_div_rbad(D);
 #if defined(__HIP_DEVICE_COMPILE__) && SX_EXACT_DIV >= 1
 #if SX_EXACT_DIV >= 2
-    const bool tiny = !(m > 0x1p-100f) && a != 0.f;
-    if (__builtin_amdgcn_ballot_w64(tiny || !(m < 0x1p100f)) == 0ull) return q2;
+    const bool tiny = !(m > 0x1p-100f && fabsf(a) > 0x1p-100f) && a != 0.f;      // (a tiny numerator: the residual would underflow)
+    if (__builtin_amdgcn_ballot_w64(tiny || !(m < 0x1p100f) || rbad) == 0ull) return q2;
     bool ok3;
     const float q3 = sx_div_scaled(a, D, &ok3);
-    const bool bad = (tiny && !ok3) || (!(m < 0x1p100f) && a != 0.f);
+    const bool bad = (tiny && !ok3) || (!(m < 0x1p100f) && a != 0.f) || rbad;
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull) return bad ? a / D.d : (tiny ? q3 : q2);
     return tiny ? q3 : q2;
 #else
-    const bool bad = !(m > 0x1p-100f && m < 0x1p100f) && a != 0.f;
+    const bool bad = (!(m > 0x1p-100f && m < 0x1p100f && fabsf(a) > 0x1p-100f) && a != 0.f) || rbad;
     if (__builtin_amdgcn_ballot_w64(bad) != 0ull) return bad ? a / D.d : q2;
 #endif
 #else
-    if (!(m > 0x1p-100f && m < 0x1p100f) && a != 0.f) return a / D.d;
+    if ((!(m > 0x1p-100f && m < 0x1p100f && fabsf(a) > 0x1p-100f) && a != 0.f) || rbad) return a / D.d;
 #endif
 #endif
     return q2;
@@ -129,15 +142,16 @@ SX_HD float sx_div(float a, const SxDiv& D) {
 // Four quotients by one loop-invariant denominator (the routing kernels' time blocks).  Default build: four sx_div.  Exact-libm build:
 // the three operations for all four, then ONE range test for the batch -- sx_div's wave-uniform guard costs a ballot and a scalar branch
 // per quotient, and in a routing super-step (8 quotients forward, 12 reverse) that was a third of the instructions -- and only a
-// wavefront that holds an out-of-range quotient goes through the guarded form.  Same results as four sx_div by construction.
+// wavefront that holds an out-of-range quotient or denominator goes through the guarded form.  Same results as four sx_div by construction.
 SX_HD void sx_div4(float* q, const float* a, const SxDiv& D) {
 #if SX_EXACT_LIBM && defined(__HIP_DEVICE_COMPILE__) && SX_EXACT_DIV >= 1
-    bool odd = false;
+    bool odd = sx_div_rbad(D);
     for (int i = 0; i < 4; ++i) {
         const float q1 = a[i] * D.r;
         q[i] = fmaf(fmaf(-D.d, q1, a[i]), D.r, q1);
+        q[i] = (a[i] == 0.f) ? q1 : q[i];
         const float m = fabsf(q[i]);
-        odd = odd || (!(m > 0x1p-100f && m < 0x1p100f) && a[i] != 0.f);
+        odd = odd || (!(m > 0x1p-100f && m < 0x1p100f && fabsf(a[i]) > 0x1p-100f) && a[i] != 0.f);
     }
     if (__builtin_amdgcn_ballot_w64(odd) == 0ull) return;
 #endif
@@ -149,7 +163,8 @@ SX_HD void sx_div4(float* q, const float* a, const SxDiv& D) {
 // operands here are always in the normal range, so the same Markstein correction as sx_div works on a reciprocal
 // refined by one Newton step from the 1-ulp hardware seed: r = RN(1/b) unless 1/b lies within 2^-46 of a rounding
 // boundary, and then q is the correctly rounded quotient.  6 instructions; mismatches against a/b are counted on
-// the device by smashx_selftest_math (tests/test_gpu_parity.py: < 1e-6 of calls, 1 ulp).
+// the device by smashx_selftest_math (tests/test_gpu_parity.py: < 1e-6 of calls, 1 ulp) and, for every normal b with a normal
+// quotient, by tests/test_gpu_math.py.  Outside that range (b beyond 2^126, subnormal or non-finite operands) it is not a division.
 SX_HD float sx_fdiv(float a, float b) {
 #if defined(__HIP_DEVICE_COMPILE__) && !SX_EXACT_LIBM
     float r = __builtin_amdgcn_rcpf(b);
@@ -210,6 +225,12 @@ SX_HD double sx_sqrt_d(float h) {
     return fma(e, 0.5 * r, s);
 }
 
+// Domain of the six fixed powers in this build: positive NORMAL arguments (measured on the device, DESIGN.md 5: within 1 ulp of the
+// correctly rounded power there, and equal to the host build of this header except in ~1e-7 of arguments, one ulp).  Outside it the
+// fp32 seeds decide: 0 and inf give NaN, and v_sqrt / v_rsq flush a subnormal argument (y^-1/4 of a subnormal y is inf on the device).
+// The kernels' arguments are parameters (cft, cst, cusl2: calibration bounds > 0), levels times parameters (ht_imd >= 1e-6,
+// sx_ops.h sx_transfer) and 1 + r^4 >= 1 (sx_production_full); x^-4 can overflow to inf for ht_imd * ct < 2.3e-10, and y^-1/4 of
+// that inf is then NaN where powf gives 0 (open: a select in the fp64 helpers measured 666 -> 686 ms on the headline).
 // powf(x, -4), powf(x, -5)   [x > 0]   (gr_transfer, md_gr_operator.f90:94-106; GR_TRANSFER_B forward_db.f90:6349-6368)
 SX_HD float sx_pow_m4(float x) { const double u = sx_rcp_d(x); const double u2 = u * u; return (float)(u2 * u2); }
 SX_HD void sx_pow_m4_m5(float x, float* m4, float* m5) {
@@ -222,7 +243,7 @@ SX_HD void sx_pow_m025_m125(float y, float* m025, float* m125) {
     const double r = sx_rquart_d(y); const double r2 = r * r;
     *m025 = (float)r; *m125 = (float)((r2 * r2) * r);
 }
-// powf(h, 3.5), powf(h, 2.5)   [h >= 0]   (gr_exchange md_gr_operator.f90:77; GR_EXCHANGE_B forward_db.f90:6155-6156)
+// powf(h, 3.5), powf(h, 2.5)   [h >= 0; h <= 0 and NaN give 0: the level is never negative]   (gr_exchange md_gr_operator.f90:77; GR_EXCHANGE_B forward_db.f90:6155-6156)
 SX_HD float sx_pow_3p5(float h) {
     if (!(h > 0.f)) return 0.f;
     const double d = (double)h; return (float)(((d * d) * d) * sx_sqrt_d(h));
@@ -362,9 +383,13 @@ SX_HD float sx_expm1f(float x) {
     const uint32_t xsb = hx & 0x80000000u;
     hx &= 0x7fffffffu;
     if (hx >= 0x4195b844u) {            // |x| >= 27 ln2
+        if (hx >= 0x42b17218u) {        // |x| >= 88.72, inf, NaN
+            if (hx > 0x7f800000u) return x + x;
+            if (hx == 0x7f800000u) return xsb ? -1.0f : x;
+            if (x > 8.8721679688e+01f) return sx_inff();                // o_threshold: overflow
+        }
         if (xsb) return -1.0f;          // fdlibm: tiny - one
-        return sx_expf(x) - one;        // never reached by tanh for |x| < 22 (2|x| < 44 < 88.7): fdlibm falls through
-    }
+    }                                   // positive x: fdlibm falls through to the reduction (tanh passes 2|x| < 44 here)
     if (hx > 0x3eb17218u) {             // |x| > 0.5 ln2
         if (hx < 0x3F851592u) {         // |x| < 1.5 ln2
             if (!xsb) { hi = x - ln2_hi; lo = ln2_lo; k = 1; }
@@ -443,6 +468,7 @@ SX_HD float sx_tanhf(float x, const bool fast = true) {      // fast = false: th
         if (ix >= 0x3f800000u) { t = sx_expm1f(2.0f * ax); z = 1.0f - sx_fdiv(2.0f, t + 2.0f); }
         else                   { t = sx_expm1f(-2.0f * ax); z = sx_fdiv(-t, t + 2.0f); }
     } else {
+        if (ix > 0x7f800000u) return x + x;       // NaN (fdlibm: one / x +- one)
         z = 1.0f - 1e-30f;
     }
     return (jx >> 31) ? -z : z;

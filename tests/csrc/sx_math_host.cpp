@@ -1,8 +1,10 @@
-/* Host build of smash_amd/csrc/sx_math.h for tests/test_sx_math.py (g++ -O2 -ffp-contract=off -mfma). */
+/* Host build of smash_amd/csrc/sx_math.h for tests/test_sx_math.py and tests/test_gpu_math.py (g++ -O2 -ffp-contract=off -mfma
+ * -fopenmp), built twice: the default build and -DSX_EXACT_LIBM=1 (tests/sx_host.py). */
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../smash_amd/csrc/sx_math.h"
 #include "../../smash_amd/csrc/sx_libm.h"
+#include "../../smash_amd/csrc/sx_selftest.h"
 
 extern "C" {
 
@@ -81,6 +83,7 @@ void sxt_div_scaled_check(long n, long* out) {
 
 float sxt_expf(float x) { return sx_expf(x); }
 
+#if !SX_EXACT_LIBM      /* (the exact build has no fp64 log2 / exp2) */
 /* sx_powf / sx_logf (fp64 log2 / exp2 evaluation) on n random arguments of the vic-a kind: out[0] = fp32 mismatches against
  * glibc powf, out[1] = against the correctly rounded logarithm (float)log((double)x), dout[0] / dout[1] = largest relative error of the fp64 values against the
  * double-precision library pow / log */
@@ -116,6 +119,8 @@ long sxt_pow_specials(void) {
     if (sx_logf(-1.f) == sx_logf(-1.f)) bad++;
     return bad;
 }
+
+#endif
 
 /* ---- exact-libm build (sx_libm.h): glibc's expf / logf / powf restated; counts of results whose BITS differ from the C library's ---- */
 long sxt_g_expf_mismatches(uint32_t lo_bits, uint32_t hi_bits, uint32_t stride) {
@@ -188,6 +193,106 @@ long sxt_g_specials(void) {
         const float a = sx_g_logf(x), b = logf(x), c = sx_g_expf(x), d = expf(x);
         if (!(sx_f2u(a) == sx_f2u(b) || (a != a && b != b))) bad++;
         if (!(sx_f2u(c) == sx_f2u(d) || (c != c && d != d))) bad++;
+    }
+    return bad;
+}
+
+/* ---- the array routines of tests/test_gpu_math.py: the same function ids as smashx_selftest_eval (include/smashx.h) ---- */
+
+/* the host build of the headers, through the same dispatch as the device kernel (smash_amd/csrc/sx_selftest.h) */
+void sxt_eval(int fn, const float* x, const float* y, long n, float* o0, float* o1) {
+    const long nt = fn == SMASHX_FN_DIV4 ? n / 4 : n;
+#pragma omp parallel for schedule(static)
+    for (long t = 0; t < nt; ++t) sx_selftest_eval1(fn, x, y, t, o0, o1);
+}
+
+/* references: kind 0 = glibc itself (tanhf, expm1f, expf, logf, powf, a / d), kind 1 = the correctly rounded value (long double
+ * tanhl / expm1l / expl / logl / powl rounded once to float; the IEEE quotient for the divisions) */
+static float sxt_ref1(int kind, float x, float y, int fn) {
+    const bool cr = kind == 1;
+    switch (fn) {
+    case SMASHX_FN_TANH: case SMASHX_FN_TANH_BRANCHY: return cr ? (float)tanhl(x) : tanhf(x);
+    case SMASHX_FN_EXPM1: return cr ? (float)expm1l(x) : expm1f(x);
+    case SMASHX_FN_EXP: return cr ? (float)expl(x) : expf(x);
+    case SMASHX_FN_LOG: return cr ? (float)logl(x) : logf(x);
+    case SMASHX_FN_POW: case SMASHX_FN_POWB: return cr ? (float)powl(x, y) : powf(x, y);
+    default: return x / y;
+    }
+}
+void sxt_ref(int kind, int fn, const float* x, const float* y, long n, float* o0, float* o1) {
+    static const float ex[13][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {-4.f, 0}, {-4.f, -5.f}, {-0.25f, 0},
+                                    {-0.25f, -1.25f}, {3.5f, 0}, {3.5f, 2.5f}};
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; ++i) {
+        const float xi = x[i];
+        if (fn >= SMASHX_FN_POW_M4 && fn <= SMASHX_FN_POW_3P5_2P5) {
+            o0[i] = kind == 1 ? (float)powl(xi, (long double)ex[fn][0]) : powf(xi, ex[fn][0]);
+            if (o1 && (fn == SMASHX_FN_POW_M4_M5 || fn == SMASHX_FN_POW_M025_M125 || fn == SMASHX_FN_POW_3P5_2P5))
+                o1[i] = kind == 1 ? (float)powl(xi, (long double)ex[fn][1]) : powf(xi, ex[fn][1]);
+        } else if (fn == SMASHX_FN_DIV4) {
+            o0[i] = xi / y[i & ~3l];
+        } else {
+            o0[i] = sxt_ref1(kind, xi, y ? y[i] : 0.f, fn);
+            if (fn == SMASHX_FN_POWB && o1) o1[i] = kind == 1 ? (float)logl(xi) : logf(xi);
+        }
+    }
+}
+
+/* a against b: out[0] = elements whose bits differ (two NaNs of any payload agree), out[1] = the largest distance in ulps (floats
+ * ordered as integers; +0 and -0 are 0 apart, a NaN against a number counts 2^32); first[0 .. nfirst) = indices of the first
+ * mismatches, -1 where there are fewer */
+static long long sxt_ord(uint32_t u) { return (u & 0x80000000u) ? -(long long)(u & 0x7fffffffu) : (long long)u; }
+void sxt_compare(const float* a, const float* b, long n, long long* out, long* first, int nfirst) {
+    long long bad = 0, worst = 0;
+#pragma omp parallel for schedule(static) reduction(+ : bad) reduction(max : worst)
+    for (long i = 0; i < n; ++i) {
+        const uint32_t ua = sx_f2u(a[i]), ub = sx_f2u(b[i]);
+        const bool na = a[i] != a[i], nb = b[i] != b[i];
+        if (na && nb) continue;
+        if (ua != ub) bad++;
+        long long d = (na || nb) ? (1ll << 32) : sxt_ord(ua) - sxt_ord(ub);
+        d = d < 0 ? -d : d;
+        if (d > worst) worst = d;
+    }
+    out[0] = bad; out[1] = worst;
+    int k = 0;
+    for (long i = 0; i < n && k < nfirst && bad > 0; ++i) {
+        const bool na = a[i] != a[i], nb = b[i] != b[i];
+        if (!(na && nb) && sx_f2u(a[i]) != sx_f2u(b[i])) first[k++] = i;
+    }
+    for (; k < nfirst; ++k) first[k] = -1;
+}
+
+/* x[i] = the float with bits lo + i * stride */
+void sxt_fill_bits(uint32_t lo, uint32_t stride, long n, float* x) {
+#pragma omp parallel for schedule(static)
+    for (long i = 0; i < n; ++i) x[i] = sx_u2f(lo + (uint32_t)i * stride);
+}
+
+/* Regression of the exact build's division guard (-DSX_EXACT_LIBM=1 library only): sx_div and sx_div4 against a / d with |d| >= 2^126
+ * (the reciprocal is subnormal) and normal quotients: the two pairs that were one ulp off, then n random pairs.  Returns the number of
+ * results whose bits differ from the IEEE quotient. */
+long sxt_div_big_denominator_mismatches(long n, unsigned seed) {
+    const float pairs[2][2] = {{0x1.9f1d2ep+108f, 0x1.e638b8p+127f}, {0x1.0efa9p+121f, 0x1.9b682ep+127f}};
+    long bad = 0;
+    for (int k = 0; k < 2; ++k) if (sx_f2u(sx_div(pairs[k][0], sx_mkdiv(pairs[k][1]))) != sx_f2u(pairs[k][0] / pairs[k][1])) bad++;
+#pragma omp parallel for schedule(static) reduction(+ : bad)
+    for (long i = 0; i < n; ++i) {
+        uint64_t h = ((uint64_t)i + 1) * 0x9E3779B97F4A7C15ull + seed;
+        h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32; h *= 0x94D049BB133111EBull; h ^= h >> 29;
+        const uint32_t ed = 253u + (uint32_t)((h >> 40) & 1u);                 /* |d| in [2^126, 2^128) */
+        const uint32_t ea = 128u + (uint32_t)((h >> 41) % 127u);               /* a in [2^1, 2^128): a / d normal */
+        const float d = sx_u2f((uint32_t)(h & 0x807fffffu) | (ed << 23));
+        const float a4[4] = {sx_u2f((uint32_t)((h >> 8) & 0x807fffffu) | (ea << 23)), sx_u2f((uint32_t)((h >> 16) & 0x007fffffu) | (ea << 23)),
+                             sx_u2f((uint32_t)((h >> 24) & 0x807fffffu) | ((ea - 1u) << 23)), sx_u2f((uint32_t)((h >> 5) & 0x007fffffu) | (ea << 23))};
+        const SxDiv D = sx_mkdiv(d);
+        float q4[4];
+        sx_div4(q4, a4, D);
+        for (int j = 0; j < 4; ++j) {
+            const float ref = a4[j] / d;
+            if (sx_f2u(sx_div(a4[j], D)) != sx_f2u(ref)) bad++;
+            if (sx_f2u(q4[j]) != sx_f2u(ref)) bad++;
+        }
     }
     return bad;
 }
