@@ -128,7 +128,7 @@ int smashx_device_count(void);
 /* ABI guard for bindings that mirror the structs by hand (the Fortran shim, ctypes): sizes in bytes of
  * {smashx_config, smashx_mesh, smashx_options, smashx_parameters, smashx_states, smashx_costs, smashx_timing};
  * returns SMASHX_ABI_VERSION. */
-#define SMASHX_ABI_VERSION 8
+#define SMASHX_ABI_VERSION 9
 int smashx_abi_sizes(int sizes[7]);
 
 /* builds the routing schedule from the mesh and allocates device storage */
@@ -185,6 +185,23 @@ int smashx_forward(smashx_plan* plan, smashx_parameters* params, const smashx_pa
 int smashx_forward_b(smashx_plan* plan, smashx_parameters* params, const smashx_parameters* params_bgd,
                      smashx_states* states, const smashx_states* states_bgd, float cost_b, float* qsim,
                      smashx_costs* costs, smashx_parameters* params_b, smashx_states* states_b);
+
+/* compute_multiple_run (mw_multiple_run.f90:68-119): nsamples forward runs that differ only in nfields spatially uniform values.
+ * Sample i replaces field ind_parameters_states[j] (1-based index into the stacked md_constant order: parameters 1..16, states
+ * 17..24) by the constant sample[j + nfields * i] over the whole grid and runs forward: res_cost[i] = cost, and, unless res_qsim is
+ * NULL, res_qsim[g + ng * (t + nt * i)] = qsim(g, t).  Every field that is not sampled keeps the caller's (distributed) values; a
+ * sampled field may be NULL.  params / states / the plan's uploaded fields and results are left untouched, whole-domain outputs are
+ * not written.  Uses the forcing, qobs and options the plan holds; computes bit for bit what nsamples calls of smashx_forward
+ * compute (same device functions; kernels in smash_amd/csrc/sx_ensemble.h: samples on the lanes, batches of samples and time
+ * chunks sized from free HBM, SMASHX_ENS_BATCH / SMASHX_ENS_CHUNK in the environment force them).
+ * SMASHX_E_UNSUPPORTED: denormalize_forward, wjreg != 0 with njr > 0, a tiled plan.  SMASHX_E_ARG: an index outside 1..24, a
+ * repeated index, a field the structure does not use, nsamples < 1, NULL res_cost / params / states. */
+int smashx_multiple_run(smashx_plan* plan, const smashx_parameters* params, const smashx_states* states, int nfields,
+                        const int* ind_parameters_states, const float* sample /* (nfields, nsamples) column-major */, int nsamples,
+                        float* res_cost /* (nsamples) */, float* res_qsim /* (ng, nt, nsamples) column-major, or NULL */);
+/* the last smashx_multiple_run of the plan: info = {samples per batch (padded to 64), steps per time chunk, batches, chunks per
+ * batch}; device_ms = time between the first and the last operation of its batches on the plan's stream (HIP events) */
+int smashx_multiple_run_info(const smashx_plan* plan, int info[4], float* device_ms);
 
 /* split-phase form of the two calls above, for measurement with inputs resident in HBM and for calibration loops:
  * upload -> (sweep)* -> download.  adjoint = 0: forward sweep; 1: forward + cost + adjoint sweep.

@@ -27,6 +27,7 @@ SYMBOLS = [
     "smashx_lbfgsb_create", "smashx_lbfgsb_step", "smashx_lbfgsb_destroy", "smashx_lbfgsb_iterations", "smashx_lbfgsb_message",
     "smashx_lbfgsb_evaluations", "smashx_lbfgsb_projected_gradient", "smashx_plan_hbm", "smashx_comm_info",
     "smashx_hyper_nhyper", "smashx_hyper_map_forward", "smashx_hyper_map_d", "smashx_hyper_map_b",
+    "smashx_multiple_run", "smashx_multiple_run_info",
 ]
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int)
@@ -113,6 +114,8 @@ def lib():
         L.smashx_lbfgsb_step.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_int)]
         for s in ("smashx_lbfgsb_destroy", "smashx_lbfgsb_iterations", "smashx_lbfgsb_message", "smashx_lbfgsb_evaluations", "smashx_lbfgsb_projected_gradient"):
             getattr(L, s).argtypes = [C.c_void_p]
+        L.smashx_multiple_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.smashx_multiple_run_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         # the structs above mirror include/smashx.h by hand: refuse a library built from another layout (a stale .so would have
         # smashx_get_timing write past the end of Timing)
         sizes = (C.c_int * 7)()

@@ -17,6 +17,7 @@
 #include "sx_cost.h"
 #include "sx_jreg.h"
 #include "sx_kernels.h"
+#include "sx_ensemble.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -431,6 +432,19 @@ struct smashx_plan {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     smashx_timing timing{};
     int last_adjoint = 0;
+    // ensemble path (smashx_multiple_run): tables built and buffers allocated on first use, all its own
+    std::vector<signed char> h_flwdir;   // D8 codes of the whole grid (0 = none), kept for the upstream tables
+    struct Ens {
+        bool tables = false;
+        int nlevels = 0; std::vector<int> level_begin;
+        int *d_up = nullptr, *d_upn = nullptr, *d_order = nullptr, *d_gauge_k = nullptr;
+        float *base = nullptr, *plane = nullptr;
+        float *sample = nullptr, *state = nullptr, *qt = nullptr, *qg = nullptr, *gj = nullptr, *med = nullptr, *cost = nullptr, *qout = nullptr;
+        size_t cap_sample = 0, cap_state = 0, cap_qt = 0, cap_qg = 0, cap_gj = 0, cap_cost = 0, cap_qout = 0;
+        hipEvent_t ev_a = nullptr, ev_b = nullptr;
+        int info[4] = {0, 0, 0, 0};      // batch size, time chunk, batches, chunks per batch of the last call
+        float device_ms = 0.f;
+    } ens;
 
     template <class T> int dmalloc(T** p, size_t count) {
         void* q = nullptr;
@@ -864,6 +878,10 @@ int smashx_plan_create(const smashx_config* cfg, const smashx_mesh* mesh, smashx
                                       rect_tile ? cfg->tile : nullptr, p->sch, mesh->owner_mask, sublevels_env());
     if (rc0 != 0) { std::string e = p->sch.error; delete p; return fail(rc0 == -5 ? SMASHX_E_MESH : SMASHX_E_ARG, e); }
     p->tiled = tiled;
+    if (!tiled) {
+        p->h_flwdir.resize((size_t)cfg->nrow * cfg->ncol);
+        for (size_t c = 0; c < p->h_flwdir.size(); ++c) { const int d = mesh->flwdir[c]; p->h_flwdir[c] = (d >= 1 && d <= 8 && mesh->active_cell[c] == 1) ? (signed char)d : 0; }
+    }
     p->n = p->sch.n; p->npad = (p->n + SX_VBLOCK - 1) / SX_VBLOCK * SX_VBLOCK;
     p->nt = cfg->nt; p->ng = cfg->ng; p->st = cfg->structure; p->n2 = (long)cfg->nrow * cfg->ncol;
     int rc = 0;
@@ -1064,6 +1082,8 @@ int smashx_plan_destroy(smashx_plan* p) {
     if (p->stream_r) (void)hipStreamDestroy(p->stream_r);
     if (p->stream_j) { (void)hipStreamSynchronize(p->stream_j); (void)hipStreamDestroy(p->stream_j); }
     if (p->ev_j) (void)hipEventDestroy(p->ev_j);
+    if (p->ens.ev_a) (void)hipEventDestroy(p->ens.ev_a);
+    if (p->ens.ev_b) (void)hipEventDestroy(p->ens.ev_b);
     delete p;
     return 0;
 }
@@ -2314,6 +2334,204 @@ int smashx_forward(smashx_plan* p, smashx_parameters* params, const smashx_param
     if ((rc = smashx_upload(p, params, params_bgd, states, states_bgd))) return rc;
     if ((rc = smashx_sweep(p, 0, 0.f))) return rc;
     return smashx_download(p, 0, params, states, qsim, costs, fstates, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// ensemble path: compute_multiple_run (mw_multiple_run.f90:68-119).  Kernels and layout: sx_ensemble.h.
+// Samples are processed in batches of SP columns (a multiple of 64) and a batch in time chunks of Tc steps: qt is
+// n x Tc x SP x 4 B, both lengths follow from free HBM unless SMASHX_ENS_BATCH / SMASHX_ENS_CHUNK force them.
+// Everything of a batch is queued on the plan's stream without a host synchronisation; the batch ends with the copies
+// of res_cost / res_qsim.  The plan's own device state (uploaded fields, states, gauge series, timing) is not touched.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+const int ENS_DROW[8] = {-1, -1, 0, 1, 1, 1, 0, -1};      // D8 codes 1..8 = N, NE, E, SE, S, SW, W, NW (sx_plan.cpp)
+const int ENS_DCOL[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+
+int ens_tables(smashx_plan* p) {
+    auto& E = p->ens;
+    if (E.tables) return 0;
+    const int n = p->n, nrow = p->cfg.nrow, ncol = p->cfg.ncol;
+    std::vector<int> up((size_t)n * 8, -1), upn(n, 0), parent(n, -1), level(n, 0), indeg(n, 0);
+    for (int k = 0; k < n; ++k) {
+        const int c = p->sch.cell_flat[k], row = c % nrow, col = c / nrow;
+        for (int i = 0; i < 8; ++i) {       // the neighbour at -D[i] drains into me iff its code == i + 1 (md_routing_operator.f90:29-31,45)
+            const int rn = row - ENS_DROW[i], cn = col - ENS_DCOL[i];
+            if (rn < 0 || rn >= nrow || cn < 0 || cn >= ncol) continue;
+            const long fn = rn + (long)cn * nrow;
+            const int ku = p->sch.k_of_flat[fn];
+            if (ku >= 0 && p->h_flwdir[fn] == i + 1) { up[(size_t)k * 8 + upn[k]++] = ku; parent[ku] = k; }
+        }
+        indeg[k] = upn[k];
+    }
+    std::vector<int> topo; topo.reserve(n);
+    for (int k = 0; k < n; ++k) if (indeg[k] == 0) topo.push_back(k);
+    for (size_t i = 0; i < topo.size(); ++i) {
+        const int k = topo[i], q = parent[k];
+        if (q >= 0) { level[q] = std::max(level[q], level[k] + 1); if (--indeg[q] == 0) topo.push_back(q); }
+    }
+    if ((int)topo.size() != n) return fail(SMASHX_E_MESH, "flow directions contain a cycle over active cells");
+    int nlev = 0;
+    for (int k = 0; k < n; ++k) nlev = std::max(nlev, level[k] + 1);
+    std::vector<int> order(n), begin(nlev + 1, 0);
+    for (int k = 0; k < n; ++k) begin[level[k] + 1]++;
+    for (int l = 0; l < nlev; ++l) begin[l + 1] += begin[l];
+    { std::vector<int> fill(begin.begin(), begin.end() - 1); for (int k = 0; k < n; ++k) order[fill[level[k]]++] = k; }
+    int rc;
+    if ((rc = p->upload_vec(&E.d_up, up)) || (rc = p->upload_vec(&E.d_upn, upn)) || (rc = p->upload_vec(&E.d_order, order))) return rc;
+    if ((rc = p->upload_vec(&E.d_gauge_k, p->sch.gauge_k.empty() ? std::vector<int>(1, 0) : p->sch.gauge_k))) return rc;
+    if ((rc = p->dmalloc(&E.base, (size_t)(SX_ENS_NP + SX_ENS_NS) * p->npad))) return rc;
+    if ((rc = p->dmalloc(&E.plane, (size_t)p->n2))) return rc;
+    HIPCHK(hipEventCreate(&E.ev_a)); HIPCHK(hipEventCreate(&E.ev_b));
+    E.nlevels = nlev; E.level_begin = begin; E.tables = true;
+    return 0;
+}
+
+int ens_grow(smashx_plan* p, float** buf, size_t* cap, size_t need) {
+    if (*cap >= need) return 0;
+    if (*buf) p->dfree(*buf);
+    *buf = nullptr; *cap = 0;
+    int rc = p->dmalloc(buf, need); if (rc) return rc;
+    *cap = need;
+    return 0;
+}
+
+int ens_env(const char* name) { const char* e = getenv(name); return e ? std::max(0, atoi(e)) : 0; }
+}  // namespace
+
+int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const smashx_states* states, int nfields,
+                        const int* ind, const float* sample, int nsamples, float* res_cost, float* res_qsim) {
+    if (!p || !params || !states || !res_cost) return fail(SMASHX_E_ARG, "smashx_multiple_run: null argument (plan, parameters, states, res_cost)");
+    if (nsamples < 1) return fail(SMASHX_E_ARG, "smashx_multiple_run: nsamples < 1");
+    if (nfields < 0 || nfields > SMASHX_GNP + SMASHX_GNS || (nfields > 0 && (!ind || !sample))) return fail(SMASHX_E_ARG, "smashx_multiple_run: bad nfields / null index list or sample");
+    const int st = p->st;
+    int smap[SX_ENS_NP + SX_ENS_NS];
+    for (int& v : smap) v = -1;
+    for (int j = 0; j < nfields; ++j) {
+        const int f = ind[j];
+        if (f < 1 || f > SMASHX_GNP + SMASHX_GNS) return fail(SMASHX_E_ARG, "smashx_multiple_run: ind_parameters_states[" + std::to_string(j) + "] = " + std::to_string(f) + " is outside 1..24");
+        const int slot = f <= SMASHX_GNP ? param_slot_of(st, f - 1) : (state_slot_of(st, f - 1 - SMASHX_GNP) < 0 ? -1 : SX_ENS_NP + state_slot_of(st, f - 1 - SMASHX_GNP));
+        if (slot < 0) return fail(SMASHX_E_ARG, "smashx_multiple_run: field " + std::to_string(f) + " is not used by the structure");
+        if (smap[slot] >= 0) return fail(SMASHX_E_ARG, "smashx_multiple_run: field " + std::to_string(f) + " is listed twice");
+        smap[slot] = j;
+    }
+    if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: denormalize_forward is not supported (the reference's multiple_run never sets it)");
+    if (p->opt.wjreg != 0.f && p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: wjreg with a regulariser (jreg_fun) is not supported");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: a tiled plan (tile / owner_mask) is not supported");
+    if (p->n > 65535 * SX_ENS_CELLS) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: more than 262140 active cells");
+    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
+    int rc = set_device(p); if (rc) return rc;
+    if ((rc = ens_tables(p))) return rc;
+    auto& X = p->ens;
+    hipStream_t sV = p->stream;
+    if ((rc = close_forcing(p))) return rc;
+    const int n = p->n, nt = p->nt, ng = p->ng;
+
+    // base fields in cell order; a sampled field needs no base
+    const dim3 b256(256), gk((n + 255) / 256);
+    int used_states = 0;
+    for (int slot = 0; slot < SX_ENS_NP + SX_ENS_NS; ++slot) {
+        const bool isp = slot < SX_ENS_NP;
+        const int f = isp ? param_field(st, slot) : state_field(st, slot - SX_ENS_NP);
+        if (f < 0) continue;
+        if (!isp) used_states |= 1 << (slot - SX_ENS_NP);
+        if (smap[slot] >= 0) continue;
+        const float* h = isp ? params->f[f] : states->f[f];
+        if (!h) return fail(SMASHX_E_ARG, std::string("smashx_multiple_run: a ") + (isp ? "parameter" : "state") + " field the structure uses is NULL and not sampled");
+        HIPCHK(hipMemcpyAsync(X.plane, h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
+        hipLaunchKernelGGL(k_gather, gk, b256, 0, sV, X.base + (size_t)slot * p->npad, X.plane, p->d_cell_flat, n);
+    }
+
+    // batch size and time chunk
+    const int SPall = (nsamples + 63) / 64 * 64;
+    const int env_b = ens_env("SMASHX_ENS_BATCH"), env_c = ens_env("SMASHX_ENS_CHUNK");
+    int SP = std::min(SPall, env_b > 0 ? (env_b + 63) / 64 * 64 : 16384);
+    int Tc = std::min(nt, env_c > 0 ? env_c : 32768);
+    {
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        const double held = 4.0 * (double)(X.cap_qt + X.cap_qg + X.cap_qout + X.cap_state);      // what a previous call already holds can be reused
+        const double budget = std::min(0.6 * ((double)fr + held), 24.0 * 1024 * 1024 * 1024);
+        auto need = [&](int sp, int tc) {
+            return 4.0 * sp * ((double)n * tc + (double)nt * std::max(ng, 1) * (res_qsim ? 2 : 1) + 5.0 * n + 64.0);
+        };
+        while (need(SP, Tc) > budget) {
+            if (env_c == 0 && Tc > 256) Tc = (Tc + 1) / 2;
+            else if (env_b == 0 && SP > 64) SP = (SP / 2 + 63) / 64 * 64;
+            else break;      // forced lengths that do not fit: the allocation below says so
+        }
+    }
+    const int nbatch = (nsamples + SP - 1) / SP, nchunk = (nt + Tc - 1) / Tc;
+    const size_t sSP = (size_t)SP;
+    if ((rc = ens_grow(p, &X.sample, &X.cap_sample, (size_t)std::max(nfields, 1) * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.state, &X.cap_state, (size_t)SX_ENS_NS * n * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.qt, &X.cap_qt, (size_t)n * Tc * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.qg, &X.cap_qg, (size_t)std::max(ng, 1) * nt * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.gj, &X.cap_gj, (size_t)2 * std::max(ng, 1) * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.cost, &X.cap_cost, sSP))) return rc;
+    if (res_qsim && ng > 0 && (rc = ens_grow(p, &X.qout, &X.cap_qout, (size_t)ng * nt * sSP))) return rc;
+
+    SxEnsArrays E{};
+    E.n = n; E.npad = p->npad; E.SP = SP; E.Tc = Tc;
+    E.base = X.base; E.sample = X.sample;
+    for (int i = 0; i < SX_ENS_NP + SX_ENS_NS; ++i) E.smap[i] = smap[i];
+    E.state = X.state; E.qt = X.qt; E.up = X.d_up; E.upn = X.d_upn; E.order = X.d_order;
+    E.qg = X.qg; E.gauge_k = X.d_gauge_k; E.gj = X.gj; E.med = X.gj + (size_t)std::max(ng, 1) * sSP; E.cost = X.cost; E.qout = X.qout;
+    const SxCostArgs C = cost_args(p, 0.f);
+    const dim3 b64(64), bV(64, SX_ENS_CELLS), gS(SP / 64);
+    const dim3 gV(SP / 64, (n + SX_ENS_CELLS - 1) / SX_ENS_CELLS);
+    std::vector<float> hs((size_t)std::max(nfields, 1) * sSP), hc(sSP);
+    X.device_ms = 0.f;
+    for (int bi = 0; bi < nbatch; ++bi) {
+        const int s0 = bi * SP, cnt = std::min(SP, nsamples - s0);
+        // sample(nfields, S) column-major -> [field][column]; the columns past the batch's last sample repeat it (whole wavefronts
+        // of ordinary values: nothing of them is ever copied out)
+        for (int j = 0; j < nfields; ++j)
+            for (int c = 0; c < SP; ++c) hs[(size_t)j * sSP + c] = sample[(size_t)j + (size_t)nfields * (s0 + std::min(c, cnt - 1))];
+        HIPCHK(hipEventRecord(X.ev_a, sV));
+        if (nfields > 0) HIPCHK(hipMemcpyAsync(X.sample, hs.data(), (size_t)nfields * sSP * 4, hipMemcpyHostToDevice, sV));
+        hipLaunchKernelGGL(sx_k_ens_init_states, dim3(SP / 64, std::min(n, 65535)), b64, 0, sV, E, used_states);
+        for (int c = 0; c < nchunk; ++c) {
+            const int t0 = c * Tc, T = std::min(Tc, nt - t0);
+            switch (st) {
+                case 1: hipLaunchKernelGGL((sx_k_ens_vert_fwd<1>), gV, bV, 0, sV, p->A, E, t0, T); break;
+                case 2: hipLaunchKernelGGL((sx_k_ens_vert_fwd<2>), gV, bV, 0, sV, p->A, E, t0, T); break;
+                case 3: hipLaunchKernelGGL((sx_k_ens_vert_fwd<3>), gV, bV, 0, sV, p->A, E, t0, T); break;
+                case 4: hipLaunchKernelGGL((sx_k_ens_vert_fwd<4>), gV, bV, 0, sV, p->A, E, t0, T); break;
+                default: hipLaunchKernelGGL(sx_k_ens_vert_fwd_vic, gV, bV, 0, sV, p->A, E, t0, T); break;
+            }
+            // one launch per level of the forest: stream order is the dependency
+            for (int l = 0; l < X.nlevels; ++l) {
+                const int i0 = X.level_begin[l], m = X.level_begin[l + 1] - i0;
+                for (int o = 0; o < m; o += 65535)
+                    hipLaunchKernelGGL(sx_k_ens_route_fwd, dim3(SP / 64, std::min(65535, m - o)), b64, 0, sV, p->A, E, i0 + o, T);
+            }
+            if (ng > 0) hipLaunchKernelGGL(sx_k_ens_gauges, dim3(SP / 64, std::min(T, 65535), ng), b64, 0, sV, E, nt, t0, T);
+        }
+        if (ng > 0) {
+            hipLaunchKernelGGL(sx_k_ens_cost_gauge, dim3(SP / 64, ng), b64, 0, sV, C, E);
+            hipLaunchKernelGGL(sx_k_ens_cost_final, gS, b64, 0, sV, C, E);
+            HIPCHK(hipMemcpyAsync(hc.data(), X.cost, (size_t)cnt * 4, hipMemcpyDeviceToHost, sV));
+            if (res_qsim) hipLaunchKernelGGL(sx_k_ens_qsim_out, dim3(SP / 64, std::min(nt, 65535)), b64, 0, sV, E, ng, nt);
+        }
+        HIPCHK(hipEventRecord(X.ev_b, sV));
+        if (res_qsim && ng > 0)
+            HIPCHK(hipMemcpyAsync(res_qsim + (size_t)s0 * nt * ng, X.qout, (size_t)cnt * nt * ng * 4, hipMemcpyDeviceToHost, sV));
+        HIPCHK(hipStreamSynchronize(sV));
+        HIPCHK(hipGetLastError());
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, X.ev_a, X.ev_b) == hipSuccess) X.device_ms += ms;
+        // cost = jobs + wjreg * jreg with jreg = 0 (mwd_cost.f90:300), as smashx_download forms it
+        for (int c = 0; c < cnt; ++c) res_cost[s0 + c] = (ng > 0 ? hc[c] : 0.f) + p->opt.wjreg * 0.f;
+    }
+    X.info[0] = SP; X.info[1] = Tc; X.info[2] = nbatch; X.info[3] = nchunk;
+    return 0;
+}
+
+int smashx_multiple_run_info(const smashx_plan* p, int info[4], float* device_ms) {
+    if (!p) return fail(SMASHX_E_ARG, "null plan");
+    if (info) for (int i = 0; i < 4; ++i) info[i] = p->ens.info[i];
+    if (device_ms) *device_ms = p->ens.device_ms;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -61,6 +61,24 @@ __device__ __forceinline__ float sx_qo(const SxCostArgs& C, int g, int t) {
     return C.qobs[(size_t)g * C.nt + t] * C.dt / ((float)C.gauge_flwacc[g] * C.dx * C.dx) * 1e3f;   // :90-92
 }
 
+// one (observed, simulated) pair folded into the running sums, in the reference's order (mwd_cost.f90:350-590); shared by
+// sx_k_cost_sums (lanes = time steps) and the ensemble cost kernel (lanes = samples, sx_ensemble.h)
+__device__ __forceinline__ void sx_sums_add(SxGaugeSums& S, float xi, float yi, bool want_lg) {
+    if (xi >= 0.f) {
+        S.n++;
+        S.sum_x = S.sum_x + xi;
+        S.sum_y = S.sum_y + yi;
+        S.sum_xx = S.sum_xx + (xi * xi);
+        S.sum_yy = S.sum_yy + (yi * yi);
+        S.sum_xy = S.sum_xy + (xi * yi);
+        S.se = S.se + (xi - yi) * (xi - yi);
+    }
+    if (want_lg && xi > 0.f && yi > 0.f) {
+        const float lgv = sx_logf(yi / xi);
+        S.lg = S.lg + xi * lgv * lgv;
+    }
+}
+
 // one wavefront per gauge
 __global__ __launch_bounds__(64) void sx_k_cost_sums(SxCostArgs C) {
     SX_LIBM_INIT();
@@ -77,19 +95,7 @@ __global__ __launch_bounds__(64) void sx_k_cost_sums(SxCostArgs C) {
             const int cnt = min(64, C.nt - tb);
             for (int i = 0; i < cnt; ++i) {
                 const float xi = __shfl(x, i), yi = __shfl(y, i);
-                if (xi >= 0.f) {
-                    S.n++;
-                    S.sum_x = S.sum_x + xi;
-                    S.sum_y = S.sum_y + yi;
-                    S.sum_xx = S.sum_xx + (xi * xi);
-                    S.sum_yy = S.sum_yy + (yi * yi);
-                    S.sum_xy = S.sum_xy + (xi * yi);
-                    S.se = S.se + (xi - yi) * (xi - yi);
-                }
-                if (want_lg && xi > 0.f && yi > 0.f) {
-                    const float lgv = sx_logf(yi / xi);
-                    S.lg = S.lg + xi * lgv * lgv;
-                }
+                sx_sums_add(S, xi, yi, want_lg);
             }
         }
     }
@@ -127,6 +133,32 @@ __device__ __forceinline__ void sx_kge_coef(const SxGaugeSums& S, const SxKge& k
     if (!(k.var_y == 0.f)) var_y_b = var_y_b + result2_b / (2.0f * sqrtf(k.var_y));
     const float mean_y_b = b_b / k.mean_x - k.mean_x * cov_b - 2.f * k.mean_y * var_y_b;
     c.kind = 4; c.c_xy = cov_b / n; c.c_yy = var_y_b / n; c.c_y = mean_y_b / n; c.c = 0.f;
+}
+
+// gauge_jobs of one gauge from its sums: the weighted criteria of compute_jobs (mwd_cost.f90:98-137); shared by sx_k_cost_final and
+// the ensemble cost kernel (sx_ensemble.h)
+__device__ __forceinline__ float sx_gauge_jobs(const SxCostArgs& C, const SxGaugeSums& S) {
+    const bool any = S.n > 0;
+    float gauge_jobs = 0.f, j_imd = 0.f;
+    for (int j = 0; j < C.njf; ++j) {
+        if (any) {
+            const float n = (float)S.n;
+            switch (C.jobs_fun[j]) {
+                case 1: { const float mean_x = S.sum_x / n;
+                          const float num = S.sum_xx - 2.f * S.sum_xy + S.sum_yy;
+                          const float den = S.sum_xx - n * mean_x * mean_x;
+                          j_imd = num / den; } break;
+                case 2: j_imd = sx_kge_value(sx_kge_components(S)); break;
+                case 3: { const float imd = sx_kge_value(sx_kge_components(S)); j_imd = imd * imd; } break;
+                case 4: j_imd = S.se; break;
+                case 5: j_imd = sqrtf(S.se / n); break;
+                case 6: j_imd = S.lg; break;
+                default: break;
+            }
+        }
+        gauge_jobs = gauge_jobs + C.wjobs_fun[j] * j_imd;
+    }
+    return gauge_jobs;
 }
 
 // single thread: per-gauge criteria, weighted sum over gauges in gauge order, adjoint coefficients
@@ -223,26 +255,7 @@ __global__ void sx_k_cost_final(SxCostArgs C, int adjoint, int phase = 0) {
         const float w = C.wgauge[g];
         if (!(w > 0.f || w < 0.f)) continue;
         const SxGaugeSums S = C.sums[g];
-        const bool any = S.n > 0;
-        float gauge_jobs = 0.f, j_imd = 0.f;
-        for (int j = 0; j < C.njf; ++j) {
-            if (any) {
-                const float n = (float)S.n;
-                switch (C.jobs_fun[j]) {
-                    case 1: { const float mean_x = S.sum_x / n;
-                              const float num = S.sum_xx - 2.f * S.sum_xy + S.sum_yy;
-                              const float den = S.sum_xx - n * mean_x * mean_x;
-                              j_imd = num / den; } break;
-                    case 2: j_imd = sx_kge_value(sx_kge_components(S)); break;
-                    case 3: { const float imd = sx_kge_value(sx_kge_components(S)); j_imd = imd * imd; } break;
-                    case 4: j_imd = S.se; break;
-                    case 5: j_imd = sqrtf(S.se / n); break;
-                    case 6: j_imd = S.lg; break;
-                    default: break;
-                }
-            }
-            gauge_jobs = gauge_jobs + C.wjobs_fun[j] * j_imd;
-        }
+        const float gauge_jobs = sx_gauge_jobs(C, S);
         if (w > 0.f) jobs = jobs + w * gauge_jobs;
         else if (phase == 1) C.medx[C.slot[g]] = gauge_jobs;
         else { arr[arr_size] = gauge_jobs; arr_b[arr_size] = 0.f; perm[arr_size] = arr_size; arr_gauge[arr_size] = g; ++arr_size; }

@@ -396,6 +396,120 @@ class Solver:
             output.cost, output.cost_jobs, output.cost_jreg = float(costs.cost), float(costs.cost_jobs), float(costs.cost_jreg)
         return float(costs.cost)
 
+    # -- ensemble ------------------------------------------------------------------------------
+    def multiple_run(self, parameters, states, sample, ind_parameters_states, return_qsim=False, *, res_cost=None, res_qsim=None):
+        """compute_multiple_run (mw_multiple_run.f90:68-119) on the plan's resident forcing, qobs and options: sample (nf, S),
+        ind_parameters_states (nf) 1-based into the stacked md_constant order (parameters 1..16, states 17..24).  Returns
+        res_cost (S,) or (res_cost, res_qsim (ng, nt, S)).  parameters / states are read only."""
+        sample, ind = check_multiple_run(self.structure, self.ng, self.nt, sample, ind_parameters_states, res_cost, res_qsim)
+        nf, S = sample.shape
+        if res_cost is None:
+            res_cost = np.zeros(S, np.float32)
+        if res_qsim is None and return_qsim:
+            res_qsim = np.zeros((self.ng, self.nt, S), np.float32, order="F")
+        want_q = res_qsim is not None and res_qsim.size > 0
+        P, k1 = _pack_const(parameters, PARAM_NAMES, _lib.Parameters)
+        St, k2 = _pack_const(states, STATE_NAMES, _lib.States)
+        _lib.check(_lib.lib().smashx_multiple_run(self._h, C.byref(P), C.byref(St), int(nf), _ptr(ind), _ptr(sample), int(S),
+                                                  _ptr(res_cost), _ptr(res_qsim) if want_q else None))
+        return (res_cost, res_qsim) if return_qsim else res_cost
+
+    def multiple_run_info(self):
+        """{batch, chunk, n_batches, n_chunks, device_ms} of the last multiple_run on this plan (smashx_multiple_run_info)."""
+        info, ms = (C.c_int * 4)(), C.c_float(0.0)
+        _lib.check(_lib.lib().smashx_multiple_run_info(self._h, info, C.byref(ms)))
+        return {"batch": info[0], "chunk": info[1], "n_batches": info[2], "n_chunks": info[3], "device_ms": float(ms.value)}
+
+
+def _pack_const(obj, names, struct_cls):
+    """Like Solver._pack for read-only fields: never rebinds an attribute of obj."""
+    s = struct_cls()
+    keep = []
+    for i, k in enumerate(names):
+        a = getattr(obj, k, None) if obj is not None else None
+        if a is None:
+            s.f[i] = None
+            continue
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.f_contiguous):
+            a = np.asfortranarray(a, dtype=np.float32)
+        keep.append(a)
+        s.f[i] = a.ctypes.data
+    return s, keep
+
+
+# fields each structure reads, stacked md_constant order 1..24 (include/smashx.h: parameters 1..16, states 17..24)
+FIELD_NAMES = tuple(PARAM_NAMES) + tuple(STATE_NAMES)
+STRUCTURE_FIELDS = {
+    "gr-a": ("cp", "cft", "exc", "lr", "hp", "hft", "hlr"),
+    "gr-b": ("ci", "cp", "cft", "exc", "lr", "hi", "hp", "hft", "hlr"),
+    "gr-c": ("ci", "cp", "cft", "cst", "exc", "lr", "hi", "hp", "hft", "hst", "hlr"),
+    "gr-d": ("cp", "cft", "lr", "hp", "hft", "hlr"),
+    "vic-a": ("b", "cusl1", "cusl2", "clsl", "ks", "ds", "dsm", "ws", "lr", "husl1", "husl2", "hlsl", "hlr"),
+}
+
+
+def check_multiple_run(structure, ng, nt, sample, ind_parameters_states, res_cost=None, res_qsim=None):
+    """Argument checks of multiple_run, before anything reaches the device (a wrong shape handed to the C call would be read or
+    written out of bounds).  Returns (sample, ind) ready for the call; raises SmashxError(E_ARG)."""
+    def bad(msg):
+        return _lib.SmashxError(_lib.E_ARG, "multiple_run: " + msg)
+    if structure not in STRUCTURE_FIELDS:
+        raise _lib.SmashxError(_lib.E_UNSUPPORTED, f"structure {structure!r} is not on the hot path yet")
+    if not isinstance(sample, np.ndarray) or sample.ndim != 2:
+        raise bad("sample must be a 2-D array (nfields, nsamples)")
+    if sample.dtype != np.float32 or not sample.flags.f_contiguous:
+        raise bad("sample must be a Fortran-ordered float32 array")
+    nf, S = sample.shape
+    if S < 1:
+        raise bad("no sample (S < 1)")
+    ind = np.asarray(ind_parameters_states)
+    if ind.ndim != 1 or ind.shape[0] != nf or not np.issubdtype(ind.dtype, np.integer):
+        raise bad(f"ind_parameters_states must hold {nf} integers, one per row of sample")
+    ind = np.ascontiguousarray(ind, np.int32)
+    if np.any(ind < 1) or np.any(ind > len(FIELD_NAMES)):
+        raise bad(f"an index is outside 1..{len(FIELD_NAMES)}")
+    if len(set(ind.tolist())) != nf:
+        raise bad("an index is repeated")
+    for i in ind:
+        if FIELD_NAMES[i - 1] not in STRUCTURE_FIELDS[structure]:
+            raise bad(f"field {FIELD_NAMES[i - 1]!r} (index {i}) is not used by {structure}")
+    if res_cost is not None:
+        if not isinstance(res_cost, np.ndarray) or res_cost.shape != (S,) or res_cost.dtype != np.float32 or not res_cost.flags.f_contiguous:
+            raise bad(f"res_cost must be a contiguous float32 array of shape ({S},)")
+    if res_qsim is not None and getattr(res_qsim, "size", 0) > 0:
+        if not isinstance(res_qsim, np.ndarray) or res_qsim.shape != (ng, nt, S) or res_qsim.dtype != np.float32 or not res_qsim.flags.f_contiguous:
+            raise bad(f"res_qsim must be empty or a Fortran-ordered float32 array of shape ({ng}, {nt}, {S})")
+    return sample, ind
+
+
+def compute_multiple_run(setup, mesh, input_data, parameters, states, output, sample, ind_parameters_states, res_cost, res_qsim):
+    """Drop-in for mw_multiple_run::compute_multiple_run (mw_multiple_run.f90:68-119), same argument order: res_cost (S,) and
+    -- unless its size is 0 -- res_qsim (ng, nt, S) are filled in place; parameters, states and output are left untouched."""
+    if res_cost is None:
+        raise _lib.SmashxError(_lib.E_ARG, "multiple_run: res_cost is None")
+    sample, ind = check_multiple_run(setup.structure, mesh.ng, setup.ntime_step, sample, ind_parameters_states, res_cost,
+                                     res_qsim if res_qsim is not None else np.zeros(0, np.float32))
+    s = _solver_for(setup, mesh, input_data)
+    s.multiple_run(parameters, states, sample, ind, res_cost=res_cost, res_qsim=res_qsim)
+    return res_cost
+
+
+def multiple_run(setup, mesh, input_data, parameters, states, sample, return_qsim=False):
+    """Convenience form: sample = {field name: 1-D array of S values}.  Returns res_cost or (res_cost, res_qsim)."""
+    if not isinstance(sample, dict) or not sample:
+        raise _lib.SmashxError(_lib.E_ARG, "multiple_run: sample must be a non-empty dict {field name: values}")
+    for k in sample:
+        if k not in FIELD_NAMES:
+            raise _lib.SmashxError(_lib.E_ARG, f"multiple_run: unknown field {k!r}")
+    cols = [np.asarray(v, np.float32).reshape(-1) for v in sample.values()]
+    if len({c.size for c in cols}) != 1:
+        raise _lib.SmashxError(_lib.E_ARG, "multiple_run: the fields of sample differ in length")
+    mat = np.asfortranarray(np.stack(cols, axis=0), dtype=np.float32)
+    ind = np.array([FIELD_NAMES.index(k) + 1 for k in sample], np.int32)
+    check_multiple_run(setup.structure, mesh.ng, setup.ntime_step, mat, ind)
+    s = _solver_for(setup, mesh, input_data)
+    return s.multiple_run(parameters, states, mat, ind, return_qsim=return_qsim)
+
 
 def _tangent_call(s, parameters, parameters_d, parameters_bgd, states, states_d, states_bgd, output, output_d):
     P, k1 = s._pack(parameters, PARAM_NAMES, _lib.Parameters)
