@@ -1,5 +1,7 @@
-"""ctypes view of include/smashx.h.  Loading fails loudly when libsmashx.so is missing: there is no
-Python / CPU implementation of the solver behind this module."""
+"""ctypes view of include/smashx.h, declared once: the header's constants, one class per struct (STRUCTS), one prototype per function
+(PROTOTYPES).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
+PROTOTYPES.  Loading fails loudly when libsmashx.so is missing: there is no Python / CPU implementation of the solver behind this
+module."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,24 +13,20 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 EXACT = os.environ.get("SMASHX_EXACT_LIBM", "0") not in ("", "0")
 LIB_PATH = os.environ.get("SMASHX_LIB", os.path.join(_HERE, "libsmashx_exact.so" if EXACT else "libsmashx.so"))
 
+# ---- the header's numeric constants, each stated once; tests/test_abi_header_cpu.py compares every one with include/smashx.h ----
+ABI_VERSION = 9
 GNP, GNS = 16, 8
-
 E_OK, E_ARG, E_UNSUPPORTED, E_HIP, E_NODEVICE, E_MESH, E_STATE = 0, -1, -2, -3, -4, -5, -6
-
-SYMBOLS = [
-    "smashx_last_error", "smashx_abi_sizes", "smashx_device_count", "smashx_plan_create", "smashx_plan_destroy", "smashx_plan_ncells",
-    "smashx_plan_cell_order", "smashx_set_forcing", "smashx_set_forcing_device_block", "smashx_set_qobs",
-    "smashx_set_options", "smashx_forward", "smashx_forward_b", "smashx_upload", "smashx_sweep", "smashx_download",
-    "smashx_get_timing", "smashx_halo_counts", "smashx_halo_edges", "smashx_plan_chunking", "smashx_set_halo", "smashx_tile_probe", "smashx_debug_group_times", "smashx_set_domain_outputs", "smashx_forward_d", "smashx_tangent_terms", "smashx_selftest_math",
-    "smashx_set_forcing_layout", "smashx_forcing_info", "smashx_control_size", "smashx_control_set", "smashx_control_get",
-    "smashx_control_gradient",
-    "smashx_comm_unique_id", "smashx_comm_create", "smashx_comm_destroy", "smashx_comm_allreduce_sum", "smashx_set_exchange",
-    "smashx_set_median_slots", "smashx_selftest_paths", "smashx_selftest_eval",
-    "smashx_lbfgsb_create", "smashx_lbfgsb_step", "smashx_lbfgsb_destroy", "smashx_lbfgsb_iterations", "smashx_lbfgsb_message",
-    "smashx_lbfgsb_evaluations", "smashx_lbfgsb_projected_gradient", "smashx_plan_hbm", "smashx_comm_info",
-    "smashx_hyper_nhyper", "smashx_hyper_map_forward", "smashx_hyper_map_d", "smashx_hyper_map_b",
-    "smashx_multiple_run", "smashx_multiple_run_info",
-]
+STRUCTURES = {"gr-a": 1, "gr-b": 2, "gr-c": 3, "gr-d": 4, "vic-a": 5}                       # SMASHX_GR_A ...
+JOBS_FUN = {"nse": 1, "kge": 2, "kge2": 3, "se": 4, "rmse": 5, "logarithmic": 6}             # SMASHX_NSE ...
+JREG_FUN = {"prior": 1, "smoothing": 2, "hard_smoothing": 3}                                  # SMASHX_PRIOR ...
+HYPER = {"hyper-linear": 1, "hyper-polynomial": 2}                                            # SMASHX_HYPER_LINEAR ...
+LBFGSB_START, LBFGSB_FG, LBFGSB_NEW_X, LBFGSB_CONVERGED, LBFGSB_ABNORMAL = range(5)
+COMM_ID_BYTES = 128
+# SMASHX_FN_*: the ids of smashx_selftest_eval
+FN = {k: i for i, k in enumerate("TANH TANH_BRANCHY EXPM1 EXP LOG POW POWB POW_M4 POW_M4_M5 POW_M025 POW_M025_M125 POW_3P5 POW_3P5_2P5 "
+                                 "DIV DIV4 FDIV DIV_FAST".split())}
+FN_COUNT = len(FN)
 
 HALO_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int)
 REDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int)
@@ -85,6 +83,79 @@ class Timing(C.Structure):
                 ("n_chained_groups", C.c_int), ("chain_staged", C.c_int)]
 
 
+# the ctypes class of every struct the header defines, by its C name
+STRUCTS = {"smashx_config": Config, "smashx_mesh": Mesh, "smashx_options": Options, "smashx_forcing_layout": ForcingLayout,
+           "smashx_hyper_map": HyperMap, "smashx_parameters": Parameters, "smashx_states": States, "smashx_costs": Costs,
+           "smashx_timing": Timing}
+
+# ---- every function of include/smashx.h: name -> (restype, argtypes), in the header's order.  Scalars as the header has them; ptr for
+# data pointers and opaque handles (it takes None, an address as int, byref(...), a ctypes array, a POINTER(...) or c_void_p instance);
+# struct parameters typed, so that byref() of another struct is refused.  tests/test_abi_header_cpu.py reads the header and compares.
+_int, _long, _llong, _uint, _float, _double, _str, ptr = C.c_int, C.c_long, C.c_longlong, C.c_uint, C.c_float, C.c_double, C.c_char_p, C.c_void_p
+_out = C.POINTER(ptr)                            # smashx_plan** / smashx_lbfgsb** / void**: where a new handle is stored
+_cfg, _mesh, _opt, _lay, _map = (C.POINTER(t) for t in (Config, Mesh, Options, ForcingLayout, HyperMap))
+_par, _sta, _cst, _tim = (C.POINTER(t) for t in (Parameters, States, Costs, Timing))
+PROTOTYPES = {
+    "smashx_last_error": (_str, []),
+    "smashx_device_count": (_int, []),
+    "smashx_abi_sizes": (_int, [ptr]),
+    "smashx_plan_create": (_int, [_cfg, _mesh, _out]),
+    "smashx_plan_destroy": (_int, [ptr]),
+    "smashx_plan_ncells": (_int, [ptr]),
+    "smashx_plan_cell_order": (_int, [ptr, ptr, ptr]),
+    "smashx_set_forcing": (_int, [ptr, ptr, ptr, _int]),
+    "smashx_set_forcing_device_block": (_int, [ptr, _int, _int, ptr, ptr]),
+    "smashx_set_forcing_layout": (_int, [ptr, _lay]),
+    "smashx_forcing_info": (_int, [ptr, ptr, ptr]),
+    "smashx_set_qobs": (_int, [ptr, ptr]),
+    "smashx_set_options": (_int, [ptr, _opt]),
+    "smashx_forward": (_int, [ptr, _par, _par, _sta, _sta, ptr, _cst, _sta]),
+    "smashx_forward_b": (_int, [ptr, _par, _par, _sta, _sta, _float, ptr, _cst, _par, _sta]),
+    "smashx_multiple_run": (_int, [ptr, _par, _sta, _int, ptr, ptr, _int, ptr, ptr]),
+    "smashx_multiple_run_info": (_int, [ptr, ptr, ptr]),
+    "smashx_upload": (_int, [ptr, _par, _par, _sta, _sta]),
+    "smashx_sweep": (_int, [ptr, _int, _float]),
+    "smashx_download": (_int, [ptr, _int, _par, _sta, ptr, _cst, _sta, _par, _sta]),
+    "smashx_get_timing": (_int, [ptr, _tim]),
+    "smashx_control_size": (_int, [ptr]),
+    "smashx_control_set": (_int, [ptr, ptr]),
+    "smashx_control_get": (_int, [ptr, ptr]),
+    "smashx_control_gradient": (_int, [ptr, ptr]),
+    "smashx_set_domain_outputs": (_int, [ptr, ptr, ptr, _int]),
+    "smashx_forward_d": (_int, [ptr, _par, _par, _par, _sta, _sta, _sta, ptr, ptr, _cst, ptr]),
+    "smashx_tangent_terms": (_int, [ptr, ptr, ptr]),
+    "smashx_tile_probe": (_int, [_cfg, _mesh, ptr, ptr, ptr, ptr, ptr, _int]),
+    "smashx_halo_counts": (_int, [ptr, ptr, ptr]),
+    "smashx_halo_edges": (_int, [ptr, ptr, ptr, ptr, ptr]),
+    "smashx_plan_chunking": (_int, [ptr, ptr, ptr]),
+    "smashx_plan_hbm": (_int, [ptr, ptr]),
+    "smashx_set_halo": (_int, [ptr, ptr, ptr, HALO_FN, ptr]),
+    "smashx_set_median_slots": (_int, [ptr, _int, ptr, REDUCE_FN, ptr]),
+    "smashx_comm_unique_id": (_int, [ptr]),
+    "smashx_comm_create": (_int, [ptr, _int, _int, _int, _out]),
+    "smashx_comm_destroy": (_int, [ptr]),
+    "smashx_comm_allreduce_sum": (_int, [ptr, ptr, _int]),
+    "smashx_comm_info": (_int, [ptr, ptr, ptr]),
+    "smashx_set_exchange": (_int, [ptr, ptr, ptr, ptr]),
+    "smashx_hyper_nhyper": (_int, [_map]),
+    "smashx_hyper_map_forward": (_int, [_map, ptr, ptr]),
+    "smashx_hyper_map_d": (_int, [_map, ptr, ptr, ptr, ptr]),
+    "smashx_hyper_map_b": (_int, [_map, ptr, ptr, ptr]),
+    "smashx_debug_group_times": (_int, [ptr, ptr, ptr]),
+    "smashx_selftest_math": (_int, [_int, _llong, _uint, _float, _float, ptr]),
+    "smashx_selftest_paths": (_int, [_int, _llong, _uint, ptr]),
+    "smashx_selftest_eval": (_int, [_int, _int, ptr, ptr, _llong, ptr, ptr]),
+    "smashx_lbfgsb_create": (_int, [_long, _int, ptr, ptr, _double, _double, _out]),
+    "smashx_lbfgsb_step": (_int, [ptr, ptr, _double, ptr, ptr]),
+    "smashx_lbfgsb_iterations": (_long, [ptr]),
+    "smashx_lbfgsb_evaluations": (_long, [ptr]),
+    "smashx_lbfgsb_projected_gradient": (_double, [ptr]),
+    "smashx_lbfgsb_message": (_str, [ptr]),
+    "smashx_lbfgsb_destroy": (_int, [ptr]),
+}
+SYMBOLS = list(PROTOTYPES)
+
+
 class SmashxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libsmashx error {code}: {msg}")
@@ -103,19 +174,9 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: build the HIP library first (__graft_entry__.build()); "
                               "smash_amd has no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        L.smashx_last_error.restype = C.c_char_p
-        for s in SYMBOLS[1:]:
-            getattr(L, s).restype = C.c_int
-        L.smashx_lbfgsb_message.restype = C.c_char_p
-        L.smashx_lbfgsb_iterations.restype = C.c_long
-        L.smashx_lbfgsb_evaluations.restype = C.c_long
-        L.smashx_lbfgsb_projected_gradient.restype = C.c_double
-        L.smashx_lbfgsb_create.argtypes = [C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_void_p)]
-        L.smashx_lbfgsb_step.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.POINTER(C.c_int)]
-        for s in ("smashx_lbfgsb_destroy", "smashx_lbfgsb_iterations", "smashx_lbfgsb_message", "smashx_lbfgsb_evaluations", "smashx_lbfgsb_projected_gradient"):
-            getattr(L, s).argtypes = [C.c_void_p]
-        L.smashx_multiple_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.smashx_multiple_run_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         # the structs above mirror include/smashx.h by hand: refuse a library built from another layout (a stale .so would have
         # smashx_get_timing write past the end of Timing)
         sizes = (C.c_int * 7)()

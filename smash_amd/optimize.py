@@ -46,27 +46,27 @@ def _lbfgsb_native(fg, x0, m, factr, pgtol, maxiter, maxfun, callback):
     n = x0.size
     lo, up = np.zeros(n, np.float64), np.ones(n, np.float64)
     h = C.c_void_p()
-    _lib.check(L.smashx_lbfgsb_create(n, int(m), lo.ctypes.data, up.ctypes.data, float(factr), float(pgtol), C.byref(h)))
+    _lib.check(L.smashx_lbfgsb_create(n, m, lo.ctypes.data, up.ctypes.data, factr, pgtol, C.byref(h)))
     try:
         x = np.array(x0, dtype=np.float64)
-        task, f, g = C.c_int(0), 0.0, np.zeros(n, np.float64)
+        task, f, g = C.c_int(_lib.LBFGSB_START), 0.0, np.zeros(n, np.float64)
         nit = nfev = 0
         stop = None
         while True:
-            _lib.check(L.smashx_lbfgsb_step(h, x.ctypes.data, float(f), g.ctypes.data, C.byref(task)))
-            if task.value == 1:                              # f and g wanted at x
+            _lib.check(L.smashx_lbfgsb_step(h, x.ctypes.data, f, g.ctypes.data, C.byref(task)))
+            if task.value == _lib.LBFGSB_FG:                # f and g wanted at x
                 # (x itself, not a copy: fg reads it before it returns and the optimiser only moves it in its next step -- 134 MB
                 # per evaluation at 1.7e7 variables)
                 f, g = fg(x)
                 g = np.ascontiguousarray(g, np.float64)
                 nfev += 1
-            elif task.value == 2:                            # new iterate
+            elif task.value == _lib.LBFGSB_NEW_X:           # new iterate
                 nit += 1
                 if callback is not None:
                     if getattr(callback, "wants_pg", False):
                         # the optimiser's own |projected gradient| at this iterate (lbfgsb.f dsave(13)) saves the callback five passes
                         # over x; such a callback copies x itself if it keeps it
-                        callback(x, float(L.smashx_lbfgsb_projected_gradient(h)))
+                        callback(x, L.smashx_lbfgsb_projected_gradient(h))
                     else:
                         callback(np.copy(x))
                 if nit >= maxiter:

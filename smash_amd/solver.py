@@ -21,7 +21,7 @@ import zlib
 import numpy as np
 
 from . import _lib
-from .types import JOBS_FUN, JREG_FUN, STRUCTURES
+from ._lib import HYPER, JOBS_FUN, JREG_FUN, STRUCTURES
 from .synth import PARAM_NAMES, STATE_NAMES
 
 
@@ -52,25 +52,59 @@ def _i32(a):
     return np.asfortranarray(a, dtype=np.int32)
 
 
+def _pack(obj, names, struct_cls, only=None, rebind=True):
+    """The fields `names` of obj (all, or those in `only`) as a smashx_parameters / smashx_states struct of pointers to Fortran-ordered
+    float32 planes, plus the arrays that must outlive the call.  A field that needs a converted copy is rebound on obj so that the
+    library's writes reach the caller; rebind=False is for read-only fields (never touches obj)."""
+    s = struct_cls()
+    keep = []
+    for i, k in enumerate(names):
+        a = getattr(obj, k, None) if obj is not None and (only is None or k in only) else None
+        if a is None:
+            s.f[i] = None
+            continue
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.f_contiguous):
+            a = np.asfortranarray(a, dtype=np.float32)
+            if rebind:
+                setattr(obj, k, a)
+        keep.append(a)
+        s.f[i] = a.ctypes.data
+    return s, keep
+
+
+def _pack_const(obj, names, struct_cls):
+    """_pack for read-only fields (tools/ensemble_bench.py and the ensemble tests call it by this name)"""
+    return _pack(obj, names, struct_cls, rebind=False)
+
+
+def _store_costs(output, qs, costs):
+    """cost terms and discharge of a finished call into output (may be None); returns the cost"""
+    if output is not None:
+        if qs is not None:
+            output.qsim = qs
+        output.cost, output.cost_jobs, output.cost_jreg = float(costs.cost), float(costs.cost_jobs), float(costs.cost_jreg)
+    return float(costs.cost)
+
+
 class Comm:
     """One RCCL communicator per process (= per GPU) for the native exchange of boundary series (include/smashx.h
     "native exchange").  Rank 0 draws the id (Comm.unique_id()); the launcher hands it to every rank."""
 
     @staticmethod
     def unique_id() -> bytes:
-        buf = (C.c_ubyte * 128)()
+        buf = (C.c_ubyte * _lib.COMM_ID_BYTES)()
         _lib.check(_lib.lib().smashx_comm_unique_id(buf))
         return bytes(buf)
 
     def __init__(self, uid: bytes, rank: int, nranks: int, device: int = -1):
-        buf = (C.c_ubyte * 128).from_buffer_copy(uid)
+        buf = (C.c_ubyte * _lib.COMM_ID_BYTES).from_buffer_copy(uid)
         self.handle = C.c_void_p()
         self.rank, self.nranks = rank, nranks
         _lib.check(_lib.lib().smashx_comm_create(buf, int(rank), int(nranks), int(device), C.byref(self.handle)))
 
     def allreduce_sum(self, values):
         v = np.ascontiguousarray(values, np.float64).copy()
-        _lib.check(_lib.lib().smashx_comm_allreduce_sum(self.handle, _ptr(v), int(v.size)))
+        _lib.check(_lib.lib().smashx_comm_allreduce_sum(self.handle, _ptr(v), v.size))
         return v
 
     def info(self):
@@ -160,12 +194,11 @@ class Solver:
     def set_forcing(self, prcp, pet, sparse=False):
         p, e = _f32(prcp), _f32(pet)
         self._fp = Solver.forcing_fingerprint(prcp, pet)
-        _lib.check(_lib.lib().smashx_set_forcing(self._h, _ptr(p), _ptr(e), int(bool(sparse))))
+        _lib.check(_lib.lib().smashx_set_forcing(self._h, _ptr(p), _ptr(e), bool(sparse)))
 
     def set_forcing_device_block(self, t0, t1, d_prcp_ptr, d_pet_ptr):
         self._forcing_external = True
-        _lib.check(_lib.lib().smashx_set_forcing_device_block(self._h, int(t0), int(t1), C.c_void_p(d_prcp_ptr),
-                                                              C.c_void_p(d_pet_ptr)))
+        _lib.check(_lib.lib().smashx_set_forcing_device_block(self._h, int(t0), int(t1), d_prcp_ptr, d_pet_ptr))
 
     def set_forcing_layout(self, compact=True, prcp_factor=0.1, pet_ratio=None, pet_hour0=1):
         """Lossless compact residency of the forcing (include/smashx.h smashx_set_forcing_layout): uint16 rain counts x
@@ -219,10 +252,7 @@ class Solver:
             if a is not None and not (a.dtype == np.float32 and a.flags.f_contiguous):
                 raise _lib.SmashxError(_lib.E_ARG, "domain outputs must be Fortran-ordered float32 arrays")
         self._dom_keep = (qsim_domain, net_prcp_domain)
-        fn = _lib.lib().smashx_set_domain_outputs
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        _lib.check(fn(self._h, None if qsim_domain is None else qsim_domain.ctypes.data,
-                      None if net_prcp_domain is None else net_prcp_domain.ctypes.data, int(bool(sparse))))
+        _lib.check(_lib.lib().smashx_set_domain_outputs(self._h, _ptr(qsim_domain), _ptr(net_prcp_domain), bool(sparse)))
 
     def tangent_terms(self):
         """(jobs_d, jreg_d) of the last forward_d on this plan (include/smashx.h smashx_tangent_terms): over a decomposition the
@@ -236,7 +266,7 @@ class Solver:
         ng = self.timing()["n_groups"]
         out = np.zeros((2, ng, 2), np.int64)
         rnd = np.zeros(ng, np.int32)
-        _lib.check(_lib.lib().smashx_debug_group_times(self._h, out.ctypes.data_as(C.POINTER(C.c_longlong)), _ptr(rnd)))
+        _lib.check(_lib.lib().smashx_debug_group_times(self._h, _ptr(out), _ptr(rnd)))
         return out, rnd
 
     def set_halo(self, out_ptr, in_ptr, fn):
@@ -249,14 +279,14 @@ class Solver:
                 traceback.print_exc()
                 return 1
         self._halo_cb = _lib.HALO_FN(tramp)
-        _lib.check(_lib.lib().smashx_set_halo(self._h, C.c_void_p(out_ptr), C.c_void_p(in_ptr), self._halo_cb, None))
+        _lib.check(_lib.lib().smashx_set_halo(self._h, out_ptr, in_ptr, self._halo_cb, None))
 
     def set_median_slots(self, nslots, slot_of_gauge, reduce_fn=None):
         """The median over the negative-weight gauges of a decomposition (include/smashx.h "cost terms that span the tiles";
         tiles.median_slots builds the arguments).  reduce_fn(values: float32 array, in place) sums the slot values over the tiles;
         not needed with the native exchange (set_exchange), which all-reduces them on the routing stream.  Call before set_options."""
         sl = np.ascontiguousarray(slot_of_gauge, np.int32) if self.ng else np.full(1, -1, np.int32)
-        cb = None
+        cb = _lib.REDUCE_FN()               # a NULL function pointer: no host reduction
         if reduce_fn is not None:
             def tramp(user, vals, n):
                 try:
@@ -269,9 +299,7 @@ class Solver:
                     return 1
             cb = _lib.REDUCE_FN(tramp)
         self._median_cb = cb
-        fn = _lib.lib().smashx_set_median_slots
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib.check(fn(self._h, int(nslots), _ptr(sl), C.cast(cb, C.c_void_p) if cb is not None else None, None))
+        _lib.check(_lib.lib().smashx_set_median_slots(self._h, int(nslots), _ptr(sl), cb, None))
 
     def set_exchange(self, comm, out_peer, in_peer):
         """Native exchange (smashx_set_exchange): comm = a Comm (or None to unset); out_peer / in_peer = the rank owning the
@@ -308,28 +336,12 @@ class Solver:
         _lib.check(_lib.lib().smashx_set_options(self._h, C.byref(o)))
 
     # -- calls ---------------------------------------------------------------------------------
-    @staticmethod
-    def _pack(obj, names, struct_cls, only=None):
-        s = struct_cls()
-        keep = []
-        for i, k in enumerate(names):
-            a = getattr(obj, k, None) if obj is not None and (only is None or k in only) else None
-            if a is None:
-                s.f[i] = None
-                continue
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.f_contiguous):
-                a = np.asfortranarray(a, dtype=np.float32)
-                setattr(obj, k, a)
-            keep.append(a)
-            s.f[i] = a.ctypes.data
-        return s, keep
-
     def upload(self, parameters, states, parameters_bgd=None, states_bgd=None, only=None):
         """only = names of the fields that changed since the last upload (the others keep their device copies)."""
-        P, k1 = self._pack(parameters, PARAM_NAMES, _lib.Parameters, only)
-        S, k2 = self._pack(states, STATE_NAMES, _lib.States, only)
-        PB, k3 = self._pack(parameters_bgd, PARAM_NAMES, _lib.Parameters) if parameters_bgd is not None else (None, None)
-        SB, k4 = self._pack(states_bgd, STATE_NAMES, _lib.States) if states_bgd is not None else (None, None)
+        P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters, only)
+        S, k2 = _pack(states, STATE_NAMES, _lib.States, only)
+        PB, k3 = _pack(parameters_bgd, PARAM_NAMES, _lib.Parameters) if parameters_bgd is not None else (None, None)
+        SB, k4 = _pack(states_bgd, STATE_NAMES, _lib.States) if states_bgd is not None else (None, None)
         _lib.check(_lib.lib().smashx_upload(self._h, C.byref(P), C.byref(PB) if PB is not None else None, C.byref(S),
                                             C.byref(SB) if SB is not None else None))
 
@@ -356,14 +368,10 @@ class Solver:
         qs = np.zeros((self.ng, self.nt), np.float32, order="F") if self.ng else None
         costs = _lib.Costs()
         _lib.check(_lib.lib().smashx_download(self._h, 0, None, None, _ptr(qs), C.byref(costs), None, None, None))
-        if output is not None:
-            if qs is not None:
-                output.qsim = qs
-            output.cost, output.cost_jobs, output.cost_jreg = float(costs.cost), float(costs.cost_jobs), float(costs.cost_jreg)
-        return float(costs.cost)
+        return _store_costs(output, qs, costs)
 
     def sweep(self, adjoint=False, cost_b=1.0):
-        _lib.check(_lib.lib().smashx_sweep(self._h, int(bool(adjoint)), C.c_float(cost_b)))
+        _lib.check(_lib.lib().smashx_sweep(self._h, bool(adjoint), cost_b))
 
     def timing(self):
         t = _lib.Timing()
@@ -375,26 +383,22 @@ class Solver:
 
     def download(self, adjoint, parameters, states, output, parameters_b=None, states_b=None, only_b=None):
         """parameters / states None: nothing but cost, discharge and gradients comes back; only_b = the gradient fields wanted."""
-        P, k1 = self._pack(parameters, PARAM_NAMES, _lib.Parameters)
-        S, k2 = self._pack(states, STATE_NAMES, _lib.States)
+        P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
+        S, k2 = _pack(states, STATE_NAMES, _lib.States)
         qs = np.zeros((self.ng, self.nt), np.float32, order="F") if self.ng else None
         costs = _lib.Costs()
         F = PB = SB = None
         kf = kp = ks = None
         if not adjoint and output is not None:
-            F, kf = self._pack(output.fstates, STATE_NAMES, _lib.States)
+            F, kf = _pack(output.fstates, STATE_NAMES, _lib.States)
         if adjoint:
-            PB, kp = self._pack(parameters_b, PARAM_NAMES, _lib.Parameters, only_b)
-            SB, ks = self._pack(states_b, STATE_NAMES, _lib.States, only_b)
-        _lib.check(_lib.lib().smashx_download(self._h, int(bool(adjoint)), C.byref(P), C.byref(S), _ptr(qs), C.byref(costs),
+            PB, kp = _pack(parameters_b, PARAM_NAMES, _lib.Parameters, only_b)
+            SB, ks = _pack(states_b, STATE_NAMES, _lib.States, only_b)
+        _lib.check(_lib.lib().smashx_download(self._h, bool(adjoint), C.byref(P), C.byref(S), _ptr(qs), C.byref(costs),
                                               C.byref(F) if F is not None else None,
                                               C.byref(PB) if PB is not None else None,
                                               C.byref(SB) if SB is not None else None))
-        if output is not None:
-            if qs is not None:
-                output.qsim = qs
-            output.cost, output.cost_jobs, output.cost_jreg = float(costs.cost), float(costs.cost_jobs), float(costs.cost_jreg)
-        return float(costs.cost)
+        return _store_costs(output, qs, costs)
 
     # -- ensemble ------------------------------------------------------------------------------
     def multiple_run(self, parameters, states, sample, ind_parameters_states, return_qsim=False, *, res_cost=None, res_qsim=None):
@@ -410,7 +414,7 @@ class Solver:
         want_q = res_qsim is not None and res_qsim.size > 0
         P, k1 = _pack_const(parameters, PARAM_NAMES, _lib.Parameters)
         St, k2 = _pack_const(states, STATE_NAMES, _lib.States)
-        _lib.check(_lib.lib().smashx_multiple_run(self._h, C.byref(P), C.byref(St), int(nf), _ptr(ind), _ptr(sample), int(S),
+        _lib.check(_lib.lib().smashx_multiple_run(self._h, C.byref(P), C.byref(St), nf, _ptr(ind), _ptr(sample), S,
                                                   _ptr(res_cost), _ptr(res_qsim) if want_q else None))
         return (res_cost, res_qsim) if return_qsim else res_cost
 
@@ -419,22 +423,6 @@ class Solver:
         info, ms = (C.c_int * 4)(), C.c_float(0.0)
         _lib.check(_lib.lib().smashx_multiple_run_info(self._h, info, C.byref(ms)))
         return {"batch": info[0], "chunk": info[1], "n_batches": info[2], "n_chunks": info[3], "device_ms": float(ms.value)}
-
-
-def _pack_const(obj, names, struct_cls):
-    """Like Solver._pack for read-only fields: never rebinds an attribute of obj."""
-    s = struct_cls()
-    keep = []
-    for i, k in enumerate(names):
-        a = getattr(obj, k, None) if obj is not None else None
-        if a is None:
-            s.f[i] = None
-            continue
-        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.f_contiguous):
-            a = np.asfortranarray(a, dtype=np.float32)
-        keep.append(a)
-        s.f[i] = a.ctypes.data
-    return s, keep
 
 
 # fields each structure reads, stacked md_constant order 1..24 (include/smashx.h: parameters 1..16, states 17..24)
@@ -512,25 +500,22 @@ def multiple_run(setup, mesh, input_data, parameters, states, sample, return_qsi
 
 
 def _tangent_call(s, parameters, parameters_d, parameters_bgd, states, states_d, states_bgd, output, output_d):
-    P, k1 = s._pack(parameters, PARAM_NAMES, _lib.Parameters)
-    PD, k2 = s._pack(parameters_d, PARAM_NAMES, _lib.Parameters)
-    PB, k3 = s._pack(parameters_bgd, PARAM_NAMES, _lib.Parameters)
-    S, k4 = s._pack(states, STATE_NAMES, _lib.States)
-    SD, k5 = s._pack(states_d, STATE_NAMES, _lib.States)
-    SB, k6 = s._pack(states_bgd, STATE_NAMES, _lib.States)
+    P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
+    PD, k2 = _pack(parameters_d, PARAM_NAMES, _lib.Parameters)
+    PB, k3 = _pack(parameters_bgd, PARAM_NAMES, _lib.Parameters)
+    S, k4 = _pack(states, STATE_NAMES, _lib.States)
+    SD, k5 = _pack(states_d, STATE_NAMES, _lib.States)
+    SB, k6 = _pack(states_bgd, STATE_NAMES, _lib.States)
     qs = np.zeros((s.ng, s.nt), np.float32, order="F") if s.ng else None
     qd = np.zeros((s.ng, s.nt), np.float32, order="F") if s.ng else None
     costs = _lib.Costs()
     cost_d = C.c_float(0.0)
     _lib.check(_lib.lib().smashx_forward_d(s._h, C.byref(P), C.byref(PD), C.byref(PB), C.byref(S), C.byref(SD), C.byref(SB),
                                            _ptr(qs), _ptr(qd), C.byref(costs), C.byref(cost_d)))
-    if output is not None:
-        if qs is not None:
-            output.qsim = qs
-        output.cost, output.cost_jobs, output.cost_jreg = float(costs.cost), float(costs.cost_jobs), float(costs.cost_jreg)
+    cost = _store_costs(output, qs, costs)
     if output_d is not None and qd is not None:
         output_d.qsim = qd
-    return float(costs.cost), float(cost_d.value)
+    return cost, float(cost_d.value)
 
 
 def invalidate_forcing(input_data):
@@ -601,14 +586,11 @@ def forward_d(setup, mesh, input_data, parameters, parameters_d, parameters_bgd,
 
 
 # ---- hyper mappings: mw_forward::hyper_forward / hyper_forward_b / hyper_forward_d (mw_forward.f90:99-181) -------------------------
-_HYPER = {"hyper-linear": 1, "hyper-polynomial": 2}
-
-
 def _hyper_map(setup, mesh, input_data, nfields, lb, ub):
-    if setup.optimize.mapping not in _HYPER:
+    if setup.optimize.mapping not in HYPER:
         raise _lib.SmashxError(_lib.E_ARG, f"setup.optimize.mapping = {setup.optimize.mapping!r}: hyper-linear or hyper-polynomial expected")
     desc = np.asfortranarray(input_data.descriptor, dtype=np.float32)
-    m = _lib.HyperMap(_HYPER[setup.optimize.mapping], mesh.nrow, mesh.ncol, int(desc.shape[2]) if desc.ndim == 3 else 0, nfields,
+    m = _lib.HyperMap(HYPER[setup.optimize.mapping], mesh.nrow, mesh.ncol, int(desc.shape[2]) if desc.ndim == 3 else 0, nfields,
                       _ptr(desc), None, None)
     keep = (desc, np.ascontiguousarray(lb, np.float32), np.ascontiguousarray(ub, np.float32))
     m.lb, m.ub = _ptr(keep[1]), _ptr(keep[2])

@@ -13,11 +13,8 @@ import copy
 
 import numpy as np
 
+from ._lib import JOBS_FUN, JREG_FUN, STRUCTURES  # noqa: F401  (the header's codes, stated in _lib.py)
 from .synth import PARAM_DEFAULTS, PARAM_NAMES, STATE_DEFAULTS, STATE_NAMES
-
-STRUCTURES = {"gr-a": 1, "gr-b": 2, "gr-c": 3, "gr-d": 4, "vic-a": 5}
-JOBS_FUN = {"nse": 1, "kge": 2, "kge2": 3, "se": 4, "rmse": 5, "logarithmic": 6}
-JREG_FUN = {"prior": 1, "smoothing": 2, "hard_smoothing": 3}
 
 # md_constant.f90:70-136
 GLB_PARAMETERS = np.array([1e-6] * 6 + [-50.0] + [1e-6] * 9, dtype=np.float32)

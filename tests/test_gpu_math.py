@@ -45,7 +45,6 @@ def device(fn, x, y=None):
     o0 = np.empty(n, np.float32)
     o1 = np.empty(n, np.float32) if fn in PAIRED else None
     f = _lib.lib().smashx_selftest_eval
-    f.argtypes = [C.c_int, C.c_int, FP, FP, C.c_longlong, FP, FP]
     _lib.check(f(0, fn, _p(x), _p(y), n, _p(o0), _p(o1)))
     return o0, o1
 

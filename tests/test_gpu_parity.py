@@ -267,7 +267,6 @@ def test_device_division_matches_ieee(blo, bhi):
     n = 200_000_000
     out = (C.c_longlong * 2)()
     fn = _lib.lib().smashx_selftest_math
-    fn.argtypes = [C.c_int, C.c_longlong, C.c_uint, C.c_float, C.c_float, C.POINTER(C.c_longlong)]
     _lib.check(fn(0, n, 12345, blo, bhi, out))
     assert out[1] == 0
     assert out[0] <= n * 1e-6, (out[0], n)
@@ -281,7 +280,6 @@ def test_wavefront_fast_paths_equal_the_branchy_forms():
     from smash_amd import _lib
     out = (C.c_longlong * 2)()
     fn = _lib.lib().smashx_selftest_paths
-    fn.argtypes = [C.c_int, C.c_longlong, C.c_uint, C.POINTER(C.c_longlong)]
     for seed in (1, 777):
         _lib.check(fn(0, 100_000_000, seed, out))
         assert out[0] == 0 and out[1] == 0, list(out)
