@@ -421,6 +421,9 @@ double smashx_lbfgsb_projected_gradient(const smashx_lbfgsb* opt);     /* infini
 const char* smashx_lbfgsb_message(const smashx_lbfgsb* opt);
 int smashx_lbfgsb_destroy(smashx_lbfgsb* opt);
 
+/* ---- model set-up on the resident forcing: declared in smashx_setup.h, which this header brings along -------------------------- */
+#include "smashx_setup.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@
 #include "sx_jreg.h"
 #include "sx_kernels.h"
 #include "sx_ensemble.h"
+#include "sx_interception.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -2531,6 +2532,59 @@ int smashx_multiple_run_info(const smashx_plan* p, int info[4], float* device_ms
     if (!p) return fail(SMASHX_E_ARG, "null plan");
     if (info) for (int i = 0; i < 4; ++i) info[i] = p->ens.info[i];
     if (device_ms) *device_ms = p->ens.device_ms;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// adjust_interception_store (mw_interception_store.f90:19-160) on the resident forcing: kernel and mapping in sx_interception.h.
+// One pass over the period per launch; the cells go in pieces of SX_ICI_PIECE so that no launch runs for more than a fraction of a
+// second at any grid size (SMASHX_ICI_PIECE in the environment overrides the piece, for experiments).
+// ---------------------------------------------------------------------------------------------------------
+#define SX_ICI_PIECE (1 << 19)
+int smashx_adjust_interception(smashx_plan* p, int nday, const int* day_index, float* ci) {
+    if (!p || !day_index || !ci) return fail(SMASHX_E_ARG, "smashx_adjust_interception: null argument (plan, day_index, ci)");
+    if (p->st != SMASHX_GR_B && p->st != SMASHX_GR_C)
+        return fail(SMASHX_E_UNSUPPORTED, "smashx_adjust_interception: the structure has no interception store (gr-b and gr-c have)");
+    const int nt = p->nt;
+    if (day_index[0] != 1) return fail(SMASHX_E_ARG, "smashx_adjust_interception: day_index must start at 1");
+    for (int t = 1; t < nt; ++t) {
+        const int d = day_index[t] - day_index[t - 1];
+        if (d != 0 && d != 1) return fail(SMASHX_E_ARG, "smashx_adjust_interception: day_index[" + std::to_string(t) + "] is not the previous day or the one after it");
+    }
+    if (day_index[nt - 1] != nday) return fail(SMASHX_E_ARG, "smashx_adjust_interception: day_index ends at " + std::to_string(day_index[nt - 1]) + ", nday = " + std::to_string(nday));
+    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
+    const int nc = sx_ici_ncand(), rows = (nc + SX_ICI_PER - 1) / SX_ICI_PER;
+    if (rows > SX_ICI_ROWS_MAX) return fail(SMASHX_E_UNSUPPORTED, "smashx_adjust_interception: more candidates than the kernel is laid out for");
+    if (p->n == 0) return 0;
+    int rc = set_device(p); if (rc) return rc;
+    if ((rc = close_forcing(p))) return rc;
+    int* d_day = nullptr; float* d_ci = nullptr;
+    if ((rc = p->dmalloc(&d_day, (size_t)nt))) return rc;
+    if ((rc = p->dmalloc(&d_ci, (size_t)p->n))) { p->dfree(d_day); return rc; }
+    const char* e = getenv("SMASHX_ICI_PIECE");
+    const int piece = std::max(64, e ? atoi(e) : SX_ICI_PIECE) / 64 * 64;
+    std::vector<float> h((size_t)p->n);
+    hipStream_t sV = p->stream;
+    hipError_t err = hipMemcpyAsync(d_day, day_index, (size_t)nt * sizeof(int), hipMemcpyHostToDevice, sV);
+    int launches = 0;
+    if (err == hipSuccess) err = hipEventRecord(p->ev0, sV);
+    for (int k0 = 0; k0 < p->n && err == hipSuccess; k0 += piece, ++launches) {
+        SxDeviceArrays A = p->A;
+        A.k0 = k0; A.k1 = std::min(p->n, k0 + piece);
+        hipLaunchKernelGGL(sx_k_adjust_interception, dim3((A.k1 - A.k0 + 63) / 64), dim3(64, rows), 0, sV, A, d_day, nc, d_ci);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipEventRecord(p->ev1, sV);
+    if (err == hipSuccess) err = hipMemcpyAsync(h.data(), d_ci, (size_t)p->n * sizeof(float), hipMemcpyDeviceToHost, sV);
+    if (err == hipSuccess) err = hipStreamSynchronize(sV);
+    p->dfree(d_day); p->dfree(d_ci);
+    if (err != hipSuccess) return fail(SMASHX_E_HIP, std::string("smashx_adjust_interception: ") + hipGetErrorString(err));
+    for (int k = 0; k < p->n; ++k) ci[p->sch.cell_flat[k]] = h[k];       // the plan's own active cells; every other element keeps its value
+    if (getenv("SMASHX_VERBOSE")) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
+        fprintf(stderr, "smashx: adjust_interception %d cells x %d steps x %d candidates: %.3f ms on the device, %d launches\n", p->n, nt, nc, ms, launches);
+    }
     return 0;
 }
 

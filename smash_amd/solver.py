@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HYPER, JOBS_FUN, JREG_FUN, STRUCTURES
-from .synth import PARAM_NAMES, STATE_NAMES
+from .synth import PARAM_DEFAULTS, PARAM_NAMES, STATE_NAMES
 
 
 # hourly share of the daily PET in the reference's reader (smash/core/_constant.py:47-75)
@@ -424,6 +424,17 @@ class Solver:
         _lib.check(_lib.lib().smashx_multiple_run_info(self._h, info, C.byref(ms)))
         return {"batch": info[0], "chunk": info[1], "n_batches": info[2], "n_chunks": info[3], "device_ms": float(ms.value)}
 
+    # -- interception capacity ---------------------------------------------------------------------
+    def adjust_interception(self, day_index, ci=None):
+        """adjust_interception_store (mw_interception_store.f90:19-160) on the plan's resident forcing: day_index (nt) is the 1-based
+        day number of every step (smash_amd.day_index builds it), nday its last entry.  Returns the (nrow, ncol) plane of capacities:
+        ci itself when given (a Fortran-ordered float32 plane; active cells the plan owns are overwritten, the others keep their
+        values), else a new plane that holds ParametersDT's default everywhere else."""
+        nday, day, ci = check_adjust_interception(self.structure, self.nrow, self.ncol, self.nt,
+                                                  int(np.asarray(day_index).reshape(-1)[-1]) if np.size(day_index) else 0, day_index, ci)
+        _lib.check(_lib.lib().smashx_adjust_interception(self._h, nday, _ptr(day), _ptr(ci)))
+        return ci
+
 
 # fields each structure reads, stacked md_constant order 1..24 (include/smashx.h: parameters 1..16, states 17..24)
 FIELD_NAMES = tuple(PARAM_NAMES) + tuple(STATE_NAMES)
@@ -499,6 +510,74 @@ def multiple_run(setup, mesh, input_data, parameters, states, sample, return_qsi
     return s.multiple_run(parameters, states, mat, ind, return_qsim=return_qsim)
 
 
+# ---- interception capacity: mw_interception_store::adjust_interception_store (mw_interception_store.f90:19-160) -------------------
+# structures with an interception store (smash/core/_constant.py STRUCTURE_ADJUST_CI)
+STRUCTURE_ADJUST_CI = {"gr-a": False, "gr-b": True, "gr-c": True, "gr-d": False, "vic-a": False}
+
+
+def day_index(start_time, end_time, dt):
+    """The day number of every time step as _build_parameters forms it (smash/core/_build_model.py:238-248): the steps are
+    start_time + dt, start_time + 2 dt, ... up to end_time (the first step is start_time + dt), a step belongs to the calendar day
+    its time stamp falls on, and the days are numbered from 1 in order of appearance.  start_time / end_time: anything
+    numpy.datetime64 takes ("2014-09-15 00:00", datetime, datetime64); dt in seconds.  Returns the int32 array (ntime_step);
+    nday is its last entry."""
+    t0, t1 = np.datetime64(start_time, "s"), np.datetime64(end_time, "s")
+    step = int(dt)
+    if step <= 0 or step != dt:
+        raise _lib.SmashxError(_lib.E_ARG, f"day_index: dt = {dt!r} must be a positive whole number of seconds")
+    nt = int((t1 - t0) // np.timedelta64(step, "s"))
+    if nt < 1:
+        raise _lib.SmashxError(_lib.E_ARG, "day_index: end_time is less than one time step after start_time")
+    stamps = t0 + np.arange(1, nt + 1) * np.timedelta64(step, "s")
+    days = stamps.astype("datetime64[D]")
+    out = np.ones(nt, np.int32)
+    out[1:] += np.cumsum(days[1:] != days[:-1])
+    return out
+
+
+def check_adjust_interception(structure, nrow, ncol, nt, nday, day_index, ci=None):
+    """Argument checks of adjust_interception, before anything reaches the C call (a short day_index would be read out of bounds,
+    a plane of another shape written out of bounds).  Returns (nday, day_index as int32, ci) ready for the call -- ci = None gives a
+    new plane filled with ParametersDT's default; raises SmashxError(E_UNSUPPORTED) for a structure without an interception store
+    and SmashxError(E_ARG) for everything else."""
+    def bad(msg):
+        return _lib.SmashxError(_lib.E_ARG, "adjust_interception: " + msg)
+    if not STRUCTURE_ADJUST_CI.get(structure, False):
+        raise _lib.SmashxError(_lib.E_UNSUPPORTED, f"adjust_interception: structure {structure!r} has no interception store")
+    day = np.asarray(day_index)
+    if day.ndim != 1 or not np.issubdtype(day.dtype, np.integer):
+        raise bad("day_index must be a 1-D integer array")
+    if day.shape[0] != nt:
+        raise bad(f"day_index holds {day.shape[0]} entries, the run has {nt} time steps")
+    if day[0] != 1:
+        raise bad(f"day_index must start at 1 (it starts at {int(day[0])})")
+    step = np.diff(day.astype(np.int64))
+    if np.any((step != 0) & (step != 1)):
+        t = int(np.flatnonzero((step != 0) & (step != 1))[0]) + 1
+        raise bad(f"day_index must be non-decreasing in steps of 0 or 1 (entry {t} is {int(day[t])} after {int(day[t - 1])})")
+    if isinstance(nday, bool) or not isinstance(nday, (int, np.integer)):
+        raise bad("nday must be an integer")
+    if int(day[-1]) != int(nday):
+        raise bad(f"day_index ends at day {int(day[-1])}, nday = {int(nday)}")
+    if ci is None:
+        ci = np.full((nrow, ncol), PARAM_DEFAULTS["ci"], np.float32, order="F")
+    elif not isinstance(ci, np.ndarray) or ci.shape != (nrow, ncol) or ci.dtype != np.float32 or not ci.flags.f_contiguous:
+        raise bad(f"ci must be a Fortran-ordered float32 array of shape ({nrow}, {ncol})")
+    return int(nday), np.ascontiguousarray(day, np.int32), ci
+
+
+def adjust_interception_store(setup, mesh, input_data, parameters, nday, day_index):
+    """Drop-in for mw_interception_store::adjust_interception_store (mw_interception_store.f90:19-160), same argument order:
+    parameters.ci is overwritten on the active cells with the capacity, out of 0.1 ... 4.9 mm, whose sub-daily interception
+    evaporation over the period comes closest to the one formed from daily totals.  The forcing is the one resident in HBM (it is
+    uploaded first when the plan does not hold it yet)."""
+    nday, day, ci = check_adjust_interception(setup.structure, mesh.nrow, mesh.ncol, setup.ntime_step, nday, day_index,
+                                              np.asfortranarray(parameters.ci, dtype=np.float32))
+    s = _solver_for(setup, mesh, input_data, options=False)
+    parameters.ci = s.adjust_interception(day, ci)
+    return parameters.ci
+
+
 def _tangent_call(s, parameters, parameters_d, parameters_bgd, states, states_d, states_bgd, output, output_d):
     P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
     PD, k2 = _pack(parameters_d, PARAM_NAMES, _lib.Parameters)
@@ -526,7 +605,7 @@ def invalidate_forcing(input_data):
         s._forcing_external = False
 
 
-def _solver_for(setup, mesh, input_data, **kw):
+def _solver_for(setup, mesh, input_data, options=True, **kw):
     s = getattr(input_data, "_smashx_solver", None)
     if s is not None and getattr(s, "_forcing_external", False):      # the caller placed the forcing in HBM itself (device blocks)
         fp = None
@@ -543,6 +622,8 @@ def _solver_for(setup, mesh, input_data, **kw):
         else:
             s.set_forcing(input_data.prcp, input_data.pet, sparse=False)
         s._fp = fp
+    if not options:       # a call that reads nothing but the forcing (adjust_interception_store)
+        return s
     if mesh.ng:
         s.set_qobs(input_data.qobs)
     s.set_options(setup.optimize)
