@@ -423,6 +423,8 @@ int smashx_lbfgsb_destroy(smashx_lbfgsb* opt);
 
 /* ---- model set-up on the resident forcing: declared in smashx_setup.h, which this header brings along -------------------------- */
 #include "smashx_setup.h"
+/* ---- statistics of the resident forcing: declared in smashx_forcing.h, likewise ---------------------------------------------------- */
+#include "smashx_forcing.h"
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,7 @@
 #include "sx_kernels.h"
 #include "sx_ensemble.h"
 #include "sx_interception.h"
+#include "sx_meanforcing.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -435,6 +436,16 @@ struct smashx_plan {
     int last_adjoint = 0;
     // ensemble path (smashx_multiple_run): tables built and buffers allocated on first use, all its own
     std::vector<signed char> h_flwdir;   // D8 codes of the whole grid (0 = none), kept for the upstream tables
+    // catchment means of the forcing (smashx_mean_forcing): D8 codes of EVERY cell of the grid, active or not (mask_upstream_cells follows
+    // them all), the per-gauge lists of plan cells on the device, the running sums between launches; built on first use
+    std::vector<signed char> h_flwdir_grid;
+    struct MeanForcing {
+        int state = 0;                   // 0 = not built, 1 = ready, 2 = refused (a catchment leaves the active cells)
+        std::string refusal;
+        std::vector<int> begin;          // ng + 1
+        int *d_list = nullptr, *d_begin = nullptr;
+        SxMfState* d_state = nullptr; float *d_mp = nullptr, *d_me = nullptr;
+    } mf;
     struct Ens {
         bool tables = false;
         int nlevels = 0; std::vector<int> level_begin;
@@ -882,6 +893,8 @@ int smashx_plan_create(const smashx_config* cfg, const smashx_mesh* mesh, smashx
     if (!tiled) {
         p->h_flwdir.resize((size_t)cfg->nrow * cfg->ncol);
         for (size_t c = 0; c < p->h_flwdir.size(); ++c) { const int d = mesh->flwdir[c]; p->h_flwdir[c] = (d >= 1 && d <= 8 && mesh->active_cell[c] == 1) ? (signed char)d : 0; }
+        p->h_flwdir_grid.resize(p->h_flwdir.size());
+        for (size_t c = 0; c < p->h_flwdir_grid.size(); ++c) { const int d = mesh->flwdir[c]; p->h_flwdir_grid[c] = (d >= 1 && d <= 8) ? (signed char)d : 0; }
     }
     p->n = p->sch.n; p->npad = (p->n + SX_VBLOCK - 1) / SX_VBLOCK * SX_VBLOCK;
     p->nt = cfg->nt; p->ng = cfg->ng; p->st = cfg->structure; p->n2 = (long)cfg->nrow * cfg->ncol;
@@ -2584,6 +2597,108 @@ int smashx_adjust_interception(smashx_plan* p, int nday, const int* day_index, f
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
         fprintf(stderr, "smashx: adjust_interception %d cells x %d steps x %d candidates: %.3f ms on the device, %d launches\n", p->n, nt, nc, ms, launches);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// compute_mean_forcing (mw_forcing_statistic.f90:18-75) on the resident forcing: kernel and mapping in sx_meanforcing.h.
+// mask_upstream_cells (mw_mask.f90:11-54) is restated here without recursion: from the gauge cell, every neighbour whose D8 code points
+// at a cell already taken is taken, over the whole grid; the mask read in flat order (row + col * nrow) IS the column-major order of
+// the reference's sum.  The lists are built on the first call and kept with the plan.  The list goes in pieces of SX_MF_PIECE entries
+// per launch, so that no launch runs for more than a fraction of a second at any grid size (SMASHX_MF_PIECE in the environment
+// overrides the piece: tests force several launches with it); the running sums live in a device buffer of the plan between launches.
+// ---------------------------------------------------------------------------------------------------------
+#define SX_MF_PIECE (1 << 20)
+namespace {
+int mf_tables(smashx_plan* p) {
+    auto& M = p->mf;
+    if (M.state == 1) return 0;
+    if (M.state == 2) return fail(SMASHX_E_UNSUPPORTED, M.refusal);
+    const int nrow = p->cfg.nrow, ncol = p->cfg.ncol, ng = p->ng;
+    const long n2 = p->n2;
+    std::vector<int> list; std::vector<char> mask((size_t)n2); std::vector<long> stack;
+    M.begin.assign(1, 0);
+    for (int g = 0; g < ng; ++g) {
+        std::fill(mask.begin(), mask.end(), 0);
+        const long c0 = p->sch.cell_flat[p->sch.gauge_k[g]];
+        mask[c0] = 1; stack.assign(1, c0);
+        while (!stack.empty()) {
+            const long c = stack.back(); stack.pop_back();
+            const int row = (int)(c % nrow), col = (int)(c / nrow);
+            for (int i = 0; i < 8; ++i) {       // the neighbour at -D[i] drains into (row, col) iff its code is i + 1
+                const int rn = row - ENS_DROW[i], cn = col - ENS_DCOL[i];
+                if (rn < 0 || rn >= nrow || cn < 0 || cn >= ncol) continue;
+                const long fn = rn + (long)cn * nrow;
+                if (p->h_flwdir_grid[fn] == i + 1 && !mask[fn]) { mask[fn] = 1; stack.push_back(fn); }
+            }
+        }
+        for (long c = 0; c < n2; ++c) {
+            if (!mask[c]) continue;
+            const int k = p->sch.k_of_flat[c];
+            if (k < 0) {
+                M.state = 2;
+                M.refusal = "smashx_mean_forcing: the catchment of gauge " + std::to_string(g) + " contains the inactive cell (" + std::to_string(c % nrow) + ", " +
+                            std::to_string(c / nrow) + "): the plan holds no forcing there";
+                M.begin.clear();
+                return fail(SMASHX_E_UNSUPPORTED, M.refusal);
+            }
+            list.push_back(k);
+        }
+        if (list.size() > (size_t)INT_MAX) return fail(SMASHX_E_UNSUPPORTED, "smashx_mean_forcing: the catchment lists of all gauges together exceed 2^31 entries");
+        M.begin.push_back((int)list.size());
+    }
+    int rc;
+    if ((rc = p->upload_vec(&M.d_list, list))) return rc;
+    if ((rc = p->upload_vec(&M.d_begin, M.begin))) return rc;
+    const size_t ntpad = (size_t)((p->nt + 63) / 64) * 64;
+    if ((rc = p->dmalloc(&M.d_state, (size_t)ng * ntpad))) return rc;
+    if ((rc = p->dmalloc(&M.d_mp, (size_t)ng * p->nt))) return rc;
+    if ((rc = p->dmalloc(&M.d_me, (size_t)ng * p->nt))) return rc;
+    M.state = 1;
+    return 0;
+}
+}  // namespace
+
+int smashx_mean_forcing(smashx_plan* p, float* mean_prcp, float* mean_pet) {
+    if (!p) return fail(SMASHX_E_ARG, "smashx_mean_forcing: null plan");
+    if (!mean_prcp && !mean_pet) return fail(SMASHX_E_ARG, "smashx_mean_forcing: both outputs are null");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_mean_forcing: a tiled plan (tile / owner_mask) is not supported: a sequential sum does not split across parts");
+    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
+    if (p->ng == 0) return 0;
+    int rc = set_device(p); if (rc) return rc;
+    if ((rc = mf_tables(p))) return rc;
+    if ((rc = close_forcing(p))) return rc;
+    auto& M = p->mf;
+    const int ng = p->ng, nt = p->nt;
+    int longest = 0;
+    for (int g = 0; g < ng; ++g) longest = std::max(longest, M.begin[g + 1] - M.begin[g]);
+    const char* e = getenv("SMASHX_MF_PIECE");
+    const int piece = std::max(64, e ? atoi(e) : SX_MF_PIECE) / 64 * 64;
+    hipStream_t sV = p->stream;
+    const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_MF_WAVES);
+    int launches = 0;
+    hipError_t err = hipEventRecord(p->ev0, sV);
+    for (long j0 = 0; j0 < longest && err == hipSuccess; j0 += piece, ++launches) {
+#define SX_MF_LAUNCH(C, P, E) hipLaunchKernelGGL((sx_k_mean_forcing<C, P, E>), grid, block, 0, sV, p->A, M.d_list, M.d_begin, ng, (int)j0, piece, M.d_state, M.d_mp, M.d_me)
+        const bool c = p->A.prcp16 != nullptr;
+        if (mean_prcp && mean_pet) { if (c) SX_MF_LAUNCH(true, true, true); else SX_MF_LAUNCH(false, true, true); }
+        else if (mean_prcp) { if (c) SX_MF_LAUNCH(true, true, false); else SX_MF_LAUNCH(false, true, false); }
+        else { if (c) SX_MF_LAUNCH(true, false, true); else SX_MF_LAUNCH(false, false, true); }
+#undef SX_MF_LAUNCH
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipEventRecord(p->ev1, sV);
+    const size_t bytes = (size_t)ng * nt * sizeof(float);
+    if (err == hipSuccess && mean_prcp) err = hipMemcpyAsync(mean_prcp, M.d_mp, bytes, hipMemcpyDeviceToHost, sV);
+    if (err == hipSuccess && mean_pet) err = hipMemcpyAsync(mean_pet, M.d_me, bytes, hipMemcpyDeviceToHost, sV);
+    if (err == hipSuccess) err = hipStreamSynchronize(sV);
+    if (err != hipSuccess) return fail(SMASHX_E_HIP, std::string("smashx_mean_forcing: ") + hipGetErrorString(err));
+    if (getenv("SMASHX_VERBOSE")) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
+        fprintf(stderr, "smashx: mean_forcing %d gauges x %d steps, longest catchment %d cells, %d list entries: %.3f ms on the device, %d launches\n", ng, nt, longest,
+                M.begin[ng], ms, launches);
     }
     return 0;
 }

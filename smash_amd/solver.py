@@ -435,6 +435,15 @@ class Solver:
         _lib.check(_lib.lib().smashx_adjust_interception(self._h, nday, _ptr(day), _ptr(ci)))
         return ci
 
+    # -- catchment means of the forcing -------------------------------------------------------------
+    def mean_forcing(self, mean_prcp=None, mean_pet=None, *, prcp=True, pet=True):
+        """compute_mean_forcing (mw_forcing_statistic.f90:18-75) on the plan's resident forcing.  Returns (mean_prcp, mean_pet), each
+        (ng, nt) float32 in Fortran order: the array given, fully overwritten, or a new one; prcp = False / pet = False leaves that
+        field out (it is then not read on the device) and returns None in its place."""
+        mp, me = check_mean_forcing(self.ng, self.nt, mean_prcp, mean_pet, prcp, pet)
+        _lib.check(_lib.lib().smashx_mean_forcing(self._h, _ptr(mp), _ptr(me)))
+        return mp, me
+
 
 # fields each structure reads, stacked md_constant order 1..24 (include/smashx.h: parameters 1..16, states 17..24)
 FIELD_NAMES = tuple(PARAM_NAMES) + tuple(STATE_NAMES)
@@ -578,6 +587,45 @@ def adjust_interception_store(setup, mesh, input_data, parameters, nday, day_ind
     return parameters.ci
 
 
+# ---- catchment means of the forcing: mw_forcing_statistic::compute_mean_forcing (mw_forcing_statistic.f90:18-75) -------------------
+def check_mean_forcing(ng, nt, mean_prcp=None, mean_pet=None, prcp=True, pet=True):
+    """Argument checks of mean_forcing, before anything reaches the C call (an array of another shape, type or order would be written
+    out of bounds or scrambled).  Returns (mean_prcp, mean_pet) ready for the call: the caller's arrays, new (ng, nt) float32 Fortran
+    arrays filled with -99 (mwd_input_data.f90:100-106) where none was given, None for a field that is left out.  Raises
+    SmashxError(E_ARG)."""
+    def bad(msg):
+        return _lib.SmashxError(_lib.E_ARG, "mean_forcing: " + msg)
+    if not prcp and not pet:
+        raise bad("neither prcp nor pet is asked for")
+    out = []
+    for name, a, want in (("mean_prcp", mean_prcp, prcp), ("mean_pet", mean_pet, pet)):
+        if not want:
+            if a is not None:
+                raise bad(f"{name} was given but the field is left out")
+            out.append(None)
+        elif a is None:
+            out.append(np.full((ng, nt), -99.0, np.float32, order="F"))
+        elif not isinstance(a, np.ndarray) or a.shape != (ng, nt) or a.dtype != np.float32 or not a.flags.f_contiguous or not a.flags.writeable:
+            raise bad(f"{name} must be a writeable Fortran-ordered float32 array of shape ({ng}, {nt})")
+        else:
+            out.append(a)
+    return out[0], out[1]
+
+
+def compute_mean_forcing(setup, mesh, input_data):
+    """Drop-in for mw_forcing_statistic::compute_mean_forcing (mw_forcing_statistic.f90:18-75), same argument order:
+    input_data.mean_prcp / mean_pet (ng, nt) are overwritten with the mean, over the cells upstream of every gauge, of the values >= 0
+    of every time step -- the reference's fp32 sum in column-major cell order, bit for bit.  The forcing is the one resident in HBM
+    (it is uploaded first when the plan does not hold it yet).  Returns (mean_prcp, mean_pet)."""
+    mp, me = check_mean_forcing(mesh.ng, setup.ntime_step, getattr(input_data, "mean_prcp", None), getattr(input_data, "mean_pet", None))
+    if mesh.ng == 0:
+        input_data.mean_prcp, input_data.mean_pet = mp, me
+        return mp, me
+    s = _solver_for(setup, mesh, input_data, options=False)
+    input_data.mean_prcp, input_data.mean_pet = s.mean_forcing(mp, me)
+    return input_data.mean_prcp, input_data.mean_pet
+
+
 def _tangent_call(s, parameters, parameters_d, parameters_bgd, states, states_d, states_bgd, output, output_d):
     P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
     PD, k2 = _pack(parameters_d, PARAM_NAMES, _lib.Parameters)
@@ -622,7 +670,7 @@ def _solver_for(setup, mesh, input_data, options=True, **kw):
         else:
             s.set_forcing(input_data.prcp, input_data.pet, sparse=False)
         s._fp = fp
-    if not options:       # a call that reads nothing but the forcing (adjust_interception_store)
+    if not options:       # a call that reads nothing but the forcing (adjust_interception_store, compute_mean_forcing)
         return s
     if mesh.ng:
         s.set_qobs(input_data.qobs)

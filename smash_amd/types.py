@@ -105,6 +105,9 @@ class Input_DataDT:
             self.prcp = np.full((mesh.nrow, mesh.ncol, nt), -99.0, np.float32, order="F")
             self.pet = np.full((mesh.nrow, mesh.ncol, nt), -99.0, np.float32, order="F")
         self.descriptor = np.full((mesh.nrow, mesh.ncol, getattr(setup, "nd", 0)), -99.0, np.float32, order="F")
+        # catchment means of the forcing (mwd_input_data.f90:100-106), filled by smash_amd.compute_mean_forcing
+        self.mean_prcp = np.full((mesh.ng, nt), -99.0, np.float32, order="F")
+        self.mean_pet = np.full((mesh.ng, nt), -99.0, np.float32, order="F")
 
 
 class _Fields:
