@@ -425,6 +425,8 @@ int smashx_lbfgsb_destroy(smashx_lbfgsb* opt);
 #include "smashx_setup.h"
 /* ---- statistics of the resident forcing: declared in smashx_forcing.h, likewise ---------------------------------------------------- */
 #include "smashx_forcing.h"
+/* ---- precipitation indices of the resident forcing: declared in smashx_prcp.h, likewise ------------------------------------------------ */
+#include "smashx_prcp.h"
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """ctypes view of include/smashx.h, declared once: the header's constants, one class per struct (STRUCTS), one prototype per function
-(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h and FORCING_PROTOTYPES for include/smashx_forcing.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
+(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h and PRCP_PROTOTYPES for include/smashx_prcp.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
 PROTOTYPES.  Loading fails loudly when libsmashx.so is missing: there is no Python / CPU implementation of the solver behind this
 module."""
 from __future__ import annotations
@@ -166,6 +166,12 @@ FORCING_PROTOTYPES = {
     "smashx_mean_forcing": (_int, [ptr, ptr, ptr]),
 }
 FORCING_SYMBOLS = list(FORCING_PROTOTYPES)
+# ---- every function of include/smashx_prcp.h (precipitation indices of the resident forcing, which smashx.h includes as well), the same
+# way; tests/test_prcp_indices_cpu.py reads that header and compares
+PRCP_PROTOTYPES = {
+    "smashx_prcp_indices": (_int, [ptr, ptr, ptr]),
+}
+PRCP_SYMBOLS = list(PRCP_PROTOTYPES)
 
 
 class SmashxError(RuntimeError):
@@ -186,7 +192,7 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: build the HIP library first (__graft_entry__.build()); "
                               "smash_amd has no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         # the structs above mirror include/smashx.h by hand: refuse a library built from another layout (a stale .so would have

@@ -20,6 +20,7 @@
 #include "sx_ensemble.h"
 #include "sx_interception.h"
 #include "sx_meanforcing.h"
+#include "sx_prcpindices.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -443,9 +444,20 @@ struct smashx_plan {
         int state = 0;                   // 0 = not built, 1 = ready, 2 = refused (a catchment leaves the active cells)
         std::string refusal;
         std::vector<int> begin;          // ng + 1
+        std::vector<int> h_list;         // the lists as uploaded (smashx_prcp_indices builds its own from them)
         int *d_list = nullptr, *d_begin = nullptr;
         SxMfState* d_state = nullptr; float *d_mp = nullptr, *d_me = nullptr;
     } mf;
+    // precipitation indices (smashx_prcp_indices): per gauge the catchment and the ten distance bins as one padded list, the catchment's
+    // distances, the gauge constants; rebuilt when the caller's flwdst plane differs from the one they were built for
+    struct PrcpIndices {
+        int state = 0;                   // 0 = not built, 1 = ready for h_flwdst
+        std::vector<float> h_flwdst;
+        std::vector<SxPiGauge> gauges;
+        long entries = 0, catchment_entries = 0;
+        int* d_list = nullptr; float *d_dl = nullptr, *d_d2l = nullptr; SxPiGauge* d_gauges = nullptr;
+        float *d_state = nullptr, *d_out = nullptr; int* d_flag = nullptr;
+    } pi;
     struct Ens {
         bool tables = false;
         int nlevels = 0; std::vector<int> level_begin;
@@ -2651,6 +2663,7 @@ int mf_tables(smashx_plan* p) {
     int rc;
     if ((rc = p->upload_vec(&M.d_list, list))) return rc;
     if ((rc = p->upload_vec(&M.d_begin, M.begin))) return rc;
+    M.h_list = std::move(list);
     const size_t ntpad = (size_t)((p->nt + 63) / 64) * 64;
     if ((rc = p->dmalloc(&M.d_state, (size_t)ng * ntpad))) return rc;
     if ((rc = p->dmalloc(&M.d_mp, (size_t)ng * p->nt))) return rc;
@@ -2699,6 +2712,165 @@ int smashx_mean_forcing(smashx_plan* p, float* mean_prcp, float* mean_pet) {
         (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
         fprintf(stderr, "smashx: mean_forcing %d gauges x %d steps, longest catchment %d cells, %d list entries: %.3f ms on the device, %d launches\n", ng, nt, longest,
                 M.begin[ng], ms, launches);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// compute_prcp_indices (mw_forcing_statistic.f90:77-220) on the resident rain: kernel and mapping in sx_prcpindices.h.
+// Host side, per gauge, as the reference does it once per call: d = flwdst - flwdst(gauge) over the WHOLE grid in fp32; the catchment
+// (the list smashx_mean_forcing builds, column-major) with its d and d * d; flwdst_qtl = quantile1d_r (m_statistic.f90:231-277) of the
+// catchment's d at q = real(i) / 100, i = 0, 10 .. 100, every operation rounded on its own; wf, the cumulated counts of the
+// catchment's d per bin; the ten bins (qtl(k-1) < d <= qtl(k)) over the whole grid, column-major inside a bin; the cell
+// (gauge_row, gauge_row), which the reference reads for pwf(1) (:181 indexes the column with the gauge's row: reproduced as written).
+// Whatever the reference would read and the plan holds no forcing for is refused.  The tables are kept with the plan and rebuilt when
+// the caller's flwdst differs from the plane they were built for.  A launch covers SX_PI_PIECE list entries of every gauge
+// (SMASHX_PI_PIECE in the environment overrides it: tests force several launches with it).
+// ---------------------------------------------------------------------------------------------------------
+#define SX_PI_PIECE (1 << 20)
+namespace {
+void pi_drop(smashx_plan* p) {
+    auto& Q = p->pi;
+    p->dfree(Q.d_list); p->dfree(Q.d_dl); p->dfree(Q.d_d2l); p->dfree(Q.d_gauges);
+    Q.d_list = nullptr; Q.d_dl = Q.d_d2l = nullptr; Q.d_gauges = nullptr;
+    Q.state = 0; Q.h_flwdst.clear(); Q.gauges.clear();
+}
+
+// quantile1d_r for the eleven quantiles; b sorted, n >= 2
+void pi_quantiles(const std::vector<float>& b, float* qtl) {
+    const int n = (int)b.size();
+    for (int i = 0; i < SX_PI_NQ; ++i) {
+        const float q = (float)(10 * i) / 100.f;
+        if (q >= 1.f) { qtl[i] = b[n - 1]; continue; }
+        const float div = q * (float)(n - 1) + 1.f;
+        const int qt = (int)floorf(div);
+        const float r = fmodf(div, (float)qt);
+        qtl[i] = (1.f - r) * b[qt - 1] + r * b[qt];
+    }
+}
+
+int pi_tables(smashx_plan* p, const float* flwdst) {
+    auto& Q = p->pi; const auto& M = p->mf;
+    const long n2 = p->n2;
+    if (Q.state == 1 && memcmp(Q.h_flwdst.data(), flwdst, (size_t)n2 * sizeof(float)) == 0) return 0;
+    pi_drop(p);
+    const int nrow = p->cfg.nrow, ncol = p->cfg.ncol, ng = p->ng;
+    auto refuse = [&](const std::string& why) { return fail(SMASHX_E_UNSUPPORTED, "smashx_prcp_indices: " + why); };
+    std::vector<int> list; std::vector<float> dl, d2l, d((size_t)n2), b; std::vector<int> bins[SX_PI_NQ];
+    std::vector<SxPiGauge> G((size_t)ng);
+    long catchment = 0;
+    for (int g = 0; g < ng; ++g) {
+        SxPiGauge& Gg = G[g];
+        const long c0 = p->sch.cell_flat[p->sch.gauge_k[g]];
+        const int row = (int)(c0 % nrow);
+        const float f0 = flwdst[c0];
+        for (long c = 0; c < n2; ++c) d[c] = flwdst[c] - f0;
+        const int nc = M.begin[g + 1] - M.begin[g];
+        if (nc < 2) return refuse("the catchment of gauge " + std::to_string(g) + " has " + std::to_string(nc) + " cell: the reference's quantile reads two");
+        const int krr = row < ncol ? p->sch.k_of_flat[row + (long)row * nrow] : -1;
+        if (krr < 0)
+            return refuse("gauge " + std::to_string(g) + ": the reference reads the rain of the cell (gauge_row, gauge_row) = (" + std::to_string(row) + ", " +
+                          std::to_string(row) + "), which is " + (row < ncol ? "inactive: the plan holds no forcing there" : "outside the grid"));
+        Gg.krr = krr; Gg.lb = (int)list.size(); Gg.db = (int)dl.size();
+        b.clear();
+        for (int j = 0; j < nc; ++j) {
+            const int k = M.h_list[(size_t)M.begin[g] + j];
+            const float dc = d[p->sch.cell_flat[k]];
+            list.push_back(k); dl.push_back(dc); d2l.push_back(dc * dc); b.push_back(dc);
+        }
+        while (list.size() % 64) { list.push_back(-1); dl.push_back(0.f); d2l.push_back(0.f); }
+        catchment += nc;
+        Gg.sec[0] = 0; Gg.sec[1] = (int)((list.size() - (size_t)Gg.lb) / 64);
+        std::sort(b.begin(), b.end());
+        float qtl[SX_PI_NQ];
+        pi_quantiles(b, qtl);
+        Gg.wf[0] = 1.f; Gg.cnt[0] = 0.f;
+        for (int k = 1; k < SX_PI_NQ; ++k) {
+            int cnt = 0;
+            for (float v : b) cnt += (v > qtl[k - 1] && v <= qtl[k]) ? 1 : 0;
+            Gg.wf[k] = Gg.wf[k - 1] + (float)cnt;
+            bins[k].clear();
+        }
+        for (long c = 0; c < n2; ++c) {                        // flat order is the column-major order of the reference's sums
+            for (int k = 1; k < SX_PI_NQ; ++k) {
+                if (!(d[c] > qtl[k - 1] && d[c] <= qtl[k])) continue;
+                const int kk = p->sch.k_of_flat[c];
+                if (kk < 0)
+                    return refuse("the inactive cell (" + std::to_string(c % nrow) + ", " + std::to_string(c / nrow) + ") lies in distance bin " + std::to_string(k) +
+                                  " of gauge " + std::to_string(g) + ": the plan holds no forcing there");
+                bins[k].push_back(kk);
+            }
+        }
+        for (int k = 1; k < SX_PI_NQ; ++k) {
+            list.insert(list.end(), bins[k].begin(), bins[k].end());
+            while (list.size() % 64) list.push_back(-1);
+            Gg.cnt[k] = (float)bins[k].size();
+            Gg.sec[k + 1] = (int)((list.size() - (size_t)Gg.lb) / 64);
+        }
+        if (list.size() > (size_t)INT_MAX - 64) return refuse("the lists of all gauges together exceed 2^31 entries");
+    }
+    int rc;
+    if ((rc = p->upload_vec(&Q.d_list, list))) return rc;
+    if ((rc = p->upload_vec(&Q.d_dl, dl))) return rc;
+    if ((rc = p->upload_vec(&Q.d_d2l, d2l))) return rc;
+    if ((rc = p->upload_vec(&Q.d_gauges, G))) return rc;
+    if (!Q.d_state) {
+        const size_t ntpad = (size_t)((p->nt + 63) / 64) * 64;
+        if ((rc = p->dmalloc(&Q.d_state, (size_t)SX_PI_NF * ng * ntpad))) return rc;
+        if ((rc = p->dmalloc(&Q.d_out, (size_t)4 * ng * p->nt))) return rc;
+        if ((rc = p->dmalloc(&Q.d_flag, (size_t)ng * p->nt))) return rc;
+    }
+    Q.h_flwdst.assign(flwdst, flwdst + n2);
+    Q.gauges = std::move(G); Q.entries = (long)list.size(); Q.catchment_entries = catchment;
+    Q.state = 1;
+    return 0;
+}
+}  // namespace
+
+int smashx_prcp_indices(smashx_plan* p, const float* flwdst, float* prcp_indices) {
+    if (!p) return fail(SMASHX_E_ARG, "smashx_prcp_indices: null plan");
+    if (!flwdst || !prcp_indices) return fail(SMASHX_E_ARG, "smashx_prcp_indices: null flwdst or prcp_indices");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_prcp_indices: a tiled plan (tile / owner_mask) is not supported: a sequential sum does not split across parts");
+    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
+    if (p->ng == 0) return 0;
+    int rc = set_device(p); if (rc) return rc;
+    if ((rc = mf_tables(p))) return rc;
+    if ((rc = pi_tables(p, flwdst))) return rc;
+    if ((rc = close_forcing(p))) return rc;
+    auto& Q = p->pi;
+    const int ng = p->ng, nt = p->nt;
+    int longest = 0;
+    for (int g = 0; g < ng; ++g) longest = std::max(longest, Q.gauges[g].sec[SX_PI_NQ]);
+    const char* e = getenv("SMASHX_PI_PIECE");
+    const int nbp = std::max(64, e ? atoi(e) : SX_PI_PIECE) / 64;
+    hipStream_t sV = p->stream;
+    const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_PI_WAVES);
+    int launches = 0;
+    hipError_t err = hipEventRecord(p->ev0, sV);
+    for (long b0 = 0; b0 < longest && err == hipSuccess; b0 += nbp, ++launches) {
+        if (p->A.prcp16 != nullptr)
+            hipLaunchKernelGGL((sx_k_prcp_indices<true>), grid, block, 0, sV, p->A, Q.d_list, Q.d_dl, Q.d_d2l, Q.d_gauges, ng, (int)b0, nbp, Q.d_state, Q.d_out, Q.d_flag);
+        else
+            hipLaunchKernelGGL((sx_k_prcp_indices<false>), grid, block, 0, sV, p->A, Q.d_list, Q.d_dl, Q.d_d2l, Q.d_gauges, ng, (int)b0, nbp, Q.d_state, Q.d_out, Q.d_flag);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipEventRecord(p->ev1, sV);
+    std::vector<float> h_out((size_t)4 * ng * nt); std::vector<int> h_flag((size_t)ng * nt);
+    if (err == hipSuccess) err = hipMemcpyAsync(h_out.data(), Q.d_out, h_out.size() * sizeof(float), hipMemcpyDeviceToHost, sV);
+    if (err == hipSuccess) err = hipMemcpyAsync(h_flag.data(), Q.d_flag, h_flag.size() * sizeof(int), hipMemcpyDeviceToHost, sV);
+    if (err == hipSuccess) err = hipStreamSynchronize(sV);
+    if (err != hipSuccess) return fail(SMASHX_E_HIP, std::string("smashx_prcp_indices: ") + hipGetErrorString(err));
+    long written = 0;
+    for (size_t o = 0; o < h_flag.size(); ++o) {               // the steps without rain stay as the caller passed them
+        if (h_flag[o] != 1) continue;
+        memcpy(prcp_indices + o * 4, h_out.data() + o * 4, 4 * sizeof(float));
+        ++written;
+    }
+    if (getenv("SMASHX_VERBOSE")) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
+        fprintf(stderr, "smashx: prcp_indices %d gauges x %d steps, longest list %d blocks, %ld list entries (%ld of catchments), %ld pairs written: %.3f ms on the device, %d launches\n",
+                ng, nt, longest, Q.entries, Q.catchment_entries, written, ms, launches);
     }
     return 0;
 }

@@ -444,6 +444,15 @@ class Solver:
         _lib.check(_lib.lib().smashx_mean_forcing(self._h, _ptr(mp), _ptr(me)))
         return mp, me
 
+    # -- precipitation indices of the forcing -------------------------------------------------------
+    def prcp_indices(self, flwdst, prcp_indices=None):
+        """compute_prcp_indices (mw_forcing_statistic.f90:77-220) on the plan's resident rain.  flwdst: (nrow, ncol) float32 Fortran
+        order (mesh.flwdst); prcp_indices: (4, ng, nt) float32 Fortran order, (std, d1, d2, vg), updated in place -- a step without rain
+        keeps its entries -- or None for a new array prefilled with -1.  Returns the array."""
+        dst, out = check_prcp_indices(self.nrow, self.ncol, self.ng, self.nt, flwdst, prcp_indices)
+        _lib.check(_lib.lib().smashx_prcp_indices(self._h, _ptr(dst), _ptr(out)))
+        return out
+
 
 # fields each structure reads, stacked md_constant order 1..24 (include/smashx.h: parameters 1..16, states 17..24)
 FIELD_NAMES = tuple(PARAM_NAMES) + tuple(STATE_NAMES)
@@ -626,6 +635,49 @@ def compute_mean_forcing(setup, mesh, input_data):
     return input_data.mean_prcp, input_data.mean_pet
 
 
+# ---- precipitation indices: mw_forcing_statistic::compute_prcp_indices (mw_forcing_statistic.f90:77-220) -----------------------------
+PRCP_INDICES = ("std", "d1", "d2", "vg")
+
+
+def check_prcp_indices(nrow, ncol, ng, nt, flwdst, prcp_indices=None):
+    """Argument checks of prcp_indices, before anything reaches the C call (an array of another shape, type or order would be read or
+    written out of bounds or scrambled).  Returns (flwdst, prcp_indices) ready for the call: the caller's arrays, or a new
+    (4, ng, nt) float32 Fortran array filled with -1 (smash/core/prcp_indices.py:112-116) where none was given.  Raises
+    SmashxError(E_ARG)."""
+    def bad(msg):
+        return _lib.SmashxError(_lib.E_ARG, "prcp_indices: " + msg)
+    if not isinstance(flwdst, np.ndarray) or flwdst.shape != (nrow, ncol) or flwdst.dtype != np.float32 or not flwdst.flags.f_contiguous:
+        raise bad(f"flwdst must be a Fortran-ordered float32 array of shape ({nrow}, {ncol})")
+    if prcp_indices is None:
+        prcp_indices = np.full((4, ng, nt), -1.0, np.float32, order="F")
+    elif (not isinstance(prcp_indices, np.ndarray) or prcp_indices.shape != (4, ng, nt) or prcp_indices.dtype != np.float32
+          or not prcp_indices.flags.f_contiguous or not prcp_indices.flags.writeable):
+        raise bad(f"prcp_indices must be a writeable Fortran-ordered float32 array of shape (4, {ng}, {nt})")
+    return flwdst, prcp_indices
+
+
+def compute_prcp_indices(setup, mesh, input_data, prcp_indices):
+    """Drop-in for mw_forcing_statistic::compute_prcp_indices (mw_forcing_statistic.f90:77-220), same argument order: prcp_indices
+    (4, ng, nt) is updated in place with (std, d1, d2, vg) of every gauge and step that has rain over the gauge's upstream cells --
+    the reference's fp32 arithmetic bit for bit, its reading of the cell (gauge_row, gauge_row) included -- and left as passed on the
+    others.  Reads mesh.flwdst and the rain resident in HBM (it is uploaded first when the plan does not hold it yet).  Returns the
+    array."""
+    dst, out = check_prcp_indices(mesh.nrow, mesh.ncol, mesh.ng, setup.ntime_step, mesh.flwdst, prcp_indices)
+    if mesh.ng == 0:
+        return out
+    s = _solver_for(setup, mesh, input_data, options=False)
+    return s.prcp_indices(dst, out)
+
+
+def prcp_indices(setup, mesh, input_data):
+    """Model.prcp_indices() of the reference (smash/core/prcp_indices.py:111-124): {"std", "d1", "d2", "vg"} -> (ng, nt) float32 arrays,
+    from a prefill of -1 with every negative entry turned into NaN."""
+    _, out = check_prcp_indices(mesh.nrow, mesh.ncol, mesh.ng, setup.ntime_step, mesh.flwdst, None)
+    compute_prcp_indices(setup, mesh, input_data, out)
+    out = np.where(out < 0, np.float32(np.nan), out)
+    return dict(zip(PRCP_INDICES, out))
+
+
 def _tangent_call(s, parameters, parameters_d, parameters_bgd, states, states_d, states_bgd, output, output_d):
     P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
     PD, k2 = _pack(parameters_d, PARAM_NAMES, _lib.Parameters)
@@ -670,7 +722,7 @@ def _solver_for(setup, mesh, input_data, options=True, **kw):
         else:
             s.set_forcing(input_data.prcp, input_data.pet, sparse=False)
         s._fp = fp
-    if not options:       # a call that reads nothing but the forcing (adjust_interception_store, compute_mean_forcing)
+    if not options:       # a call that reads nothing but the forcing (adjust_interception_store, compute_mean_forcing, compute_prcp_indices)
         return s
     if mesh.ng:
         s.set_qobs(input_data.qobs)

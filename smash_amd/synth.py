@@ -104,6 +104,40 @@ def flow_accumulation(flwdir: np.ndarray, active: np.ndarray | None = None) -> n
     return np.asfortranarray(out)
 
 
+def flow_distance(flwdir: np.ndarray, active: np.ndarray | None, dx: float) -> np.ndarray:
+    """mesh%flwdst: the length of the D8 path from each active cell down to the cell where the water leaves the active domain
+    (the statement of mw_meshing.f90:325-420: 0 at the outlet, + dx per straight step and + sqrt(2 dx dx) per diagonal step going
+    upstream, every addition in float32, -99 elsewhere).  An outlet is a cell downstream_index() gives no receiver: it drains off
+    the grid, into an inactive cell, or closes a pit pair.  One numpy pass per topological level, from the outlets upwards."""
+    nrow, ncol = flwdir.shape
+    f32 = np.float32
+    ds, ok = downstream_index(flwdir, active)
+    n = nrow * ncol
+    straight = f32(dx)
+    diagonal = np.sqrt(f32(2.0) * f32(dx) * f32(dx), dtype=f32)
+    step = np.where(np.asarray(flwdir).reshape(-1) % 2 == 1, straight, diagonal).astype(f32)      # codes 1, 3, 5, 7 are straight
+    out = np.full(n, -99.0, f32)
+    src = np.flatnonzero(ds >= 0)
+    src = src[np.argsort(ds[src], kind="stable")]
+    key = ds[src]
+    cells = np.arange(n)
+    first, last = np.searchsorted(key, cells, side="left"), np.searchsorted(key, cells, side="right")
+    front = np.flatnonzero(ok & (ds < 0))
+    out[front] = f32(0.0)
+    while front.size:
+        cnt = last[front] - first[front]
+        front = front[cnt > 0]
+        cnt = cnt[cnt > 0]
+        if not front.size:
+            break
+        parent = np.repeat(front, cnt)
+        offs = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        child = src[np.repeat(first[front], cnt) + offs]
+        out[child] = out[parent] + step[child]
+        front = child
+    return np.asfortranarray(out.reshape(nrow, ncol))
+
+
 def make_path(flwacc: np.ndarray) -> np.ndarray:
     """Cell visiting order = ascending flow accumulation (reference meshing.py:216-224); 0-based
     (2, nrow*ncol) like the Python side of the reference sees it."""

@@ -79,10 +79,27 @@ class MeshDT:
         self.active_cell = np.ones((nrow, ncol), np.int32, order="F")
         self.gauge_pos = np.zeros((ng, 2), np.int32, order="F")
         self.area = np.zeros(ng, np.float32)
+        self._flwdst = None
 
     @property
     def nac(self):
         return int(np.count_nonzero(self.active_cell == 1))
+
+    @property
+    def flwdst(self):
+        """flow distances to the outlet(s) (mwd_mesh.f90:64), (nrow, ncol) float32, -99 until set; a mesh made by from_synth fills it
+        on first use with synth.flow_distance of its own flow directions (smash_amd.compute_prcp_indices reads it)"""
+        if self._flwdst is None:
+            if getattr(self, "_flwdst_from_synth", False):
+                from . import synth
+                self._flwdst = synth.flow_distance(self.flwdir, self.active_cell, self.dx)
+            else:
+                self._flwdst = np.full((self.nrow, self.ncol), -99.0, np.float32, order="F")
+        return self._flwdst
+
+    @flwdst.setter
+    def flwdst(self, value):
+        self._flwdst = value
 
     @classmethod
     def from_synth(cls, setup, m):
@@ -90,6 +107,7 @@ class MeshDT:
         o.dx = m.dx
         o.flwdir, o.flwacc, o.path, o.active_cell = m.flwdir, m.flwacc, m.path, m.active_cell
         o.gauge_pos, o.area = m.gauge_pos, m.area
+        o._flwdst_from_synth = True
         return o
 
 
