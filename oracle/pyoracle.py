@@ -38,9 +38,9 @@ class _Prefixed:
     """liboracle64.so exports orc64_*: present them under the names run() uses."""
 
     def __init__(self, dll):
-        for k in ("forward", "forward_b", "forward_d", "set_domain_outputs"):
+        for k in ("forward", "forward_b", "forward_d", "set_domain_outputs", "census"):
             f = getattr(dll, "orc64_" + k)
-            f.restype = C.c_int if k != "set_domain_outputs" else None
+            f.restype = C.c_int if k not in ("set_domain_outputs", "census") else None
             setattr(self, "orc_" + k, f)
 
 
@@ -74,14 +74,34 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# the counters of orc_census, in the order of the ORC_CEN_* enum (oracle/smash_oracle.h, where each is defined)
+CENSUS = ("cell_steps", "gap", "pn_pos", "en_pos", "ei_store", "pn_interception", "tanh_sat", "hp_big", "perc_pow",
+          "gap_pwx3_nonpos", "hft_floor", "hst_floor", "qd_zero", "still", "calm_not_still",
+          "vic_rain", "vic_wusl_low", "vic_wusl_high", "vic_ifl_full", "vic_ifl_prcp", "vic_usl1_full", "vic_usl2_full",
+          "vic_bc_room", "vic_bc_limited", "vic_evap_store", "vic_pet_spent", "vic_above_ws", "vic_qb_store")
+GR_CENSUS = CENSUS[2:15]          # counted by the gr structures only (ei_store, pn_interception: gr-b, gr-c; hst_floor: gr-c)
+VIC_CENSUS = CENSUS[15:]          # counted by vic-a only
+
+
+def census(fp64=False):
+    """Branch census of the last forward run (run(...) without adjoint / params_d) of that precision: dict name -> cell-steps."""
+    L = lib64() if fp64 else lib()
+    n = np.zeros(len(CENSUS), np.int64)
+    L.orc_census.restype = None
+    L.orc_census(_p(n))
+    return dict(zip(CENSUS, (int(v) for v in n)))
+
+
 def run(structure, mesh, dt, prcp, pet, qobs, params, states, *, adjoint=False, params_bgd=None,
         states_bgd=None, denormalize_forward=False, optimize_start_step=1, jobs_fun=("nse",),
         wjobs_fun=(1.0,), jreg_fun=(), wjreg_fun=(), wjreg=0.0, wgauge=None, optim_parameters=None,
         optim_states=None, lb_parameters=None, ub_parameters=None, lb_states=None, ub_states=None,
-        cost_b=1.0, save_domain=False, params_d=None, states_d=None, fp64=False):
+        cost_b=1.0, save_domain=False, params_d=None, states_d=None, fp64=False, reference_max=False):
     """Same calling convention and result dict as oracle.refbind.run (dense forcing only).
     save_domain: also return qsim_domain / net_prcp_domain (nrow, ncol, nt), -99 on inactive cells.
     params_d / states_d (dicts): run the tangent model (orc_forward_d) along that direction -> cost_d, qsim_d.
+    reference_max (forward run only): MAX / MIN with a NaN operand as the flang build of the reference evaluates them
+    (orc_set_reference_max, oracle/smash_oracle.h).
     fp64: evaluate the same statements in double (liboracle64.so) -- the common "truth" the fp32 builds are ranked against
     (tools/accuracy_report.py); inputs are the fp32 values, widened."""
     from smash_amd.synth import PARAM_NAMES, STATE_NAMES
@@ -144,6 +164,10 @@ def run(structure, mesh, dt, prcp, pet, qobs, params, states, *, adjoint=False, 
         qdom = np.full((nrow, ncol, nt), -99.0, npreal, order="F")
         pdom = np.full((nrow, ncol, nt), -99.0, npreal, order="F")
         L.orc_set_domain_outputs(_p(qdom), _p(pdom))
+    if reference_max:
+        assert not adjoint and not fp64
+        L.orc_set_reference_max.restype = None
+        L.orc_set_reference_max(1)
     try:
         if adjoint:
             rc = L.orc_forward_b(*common, real(cost_b), _p(qsim), _p(costs), _p(p_b), _p(s_b))
@@ -151,6 +175,8 @@ def run(structure, mesh, dt, prcp, pet, qobs, params, states, *, adjoint=False, 
             rc = L.orc_forward(*common, _p(qsim), _p(costs), _p(fstates))
     finally:
         L.orc_set_domain_outputs(None, None)
+        if reference_max:
+            L.orc_set_reference_max(0)
     if rc != 0:
         raise RuntimeError(f"oracle returned {rc}")
     return dict(qsim_domain=qdom, net_prcp_domain=pdom,

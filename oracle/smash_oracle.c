@@ -14,13 +14,36 @@
 #include <string.h>
 
 /* ------------------------------------------------------------------------------------------- */
+/* branch census: which regimes the cell-steps of the last orc_forward reached (smash_oracle.h). */
+/* Comparisons on values the statements have already computed; nothing below feeds the arithmetic. */
+/* ------------------------------------------------------------------------------------------- */
+static long long g_cen[ORC_CEN_N];
+static int g_cen_on = 0;              /* only inside orc_forward's sweep: the adjoint recomputes the operators */
+#define CEN(i, cond) do { if (g_cen_on && (cond)) g_cen[i]++; } while (0)
+void orc_census(long long* out) { for (int i = 0; i < ORC_CEN_N; ++i) out[i] = g_cen[i]; }
+
+/* ------------------------------------------------------------------------------------------- */
+/* MAX / MIN with a NaN operand.  The Fortran standard leaves them to the processor.  Default: C's fmaxf / fminf, which return
+ * the other operand -- the same outcome as the IF forms into which Tapenade rewrites every MAX / MIN of the operators in
+ * forward_db.f90 (the code base_forward_b and base_forward_d run).  orc_set_reference_max(1): as the flang build of the
+ * reference evaluates the intrinsics of the ORIGINAL operators that base_forward runs, (a > b) ? a : b -- the second operand
+ * whenever either is NaN.  The two agree bit for bit on ordered operands. */
+/* ------------------------------------------------------------------------------------------- */
+static int g_ref_max = 0;
+void orc_set_reference_max(int on) { g_ref_max = on; }
+static float orc_max(float a, float b) { return g_ref_max ? (a > b ? a : b) : fmaxf(a, b); }
+static float orc_min(float a, float b) { return g_ref_max ? (a < b ? a : b) : fminf(a, b); }
+
+/* ------------------------------------------------------------------------------------------- */
 /* operators: smash/solver/operator/md_gr_operator.f90, md_routing_operator.f90                 */
 /* ------------------------------------------------------------------------------------------- */
 
 /* md_gr_operator.f90:20-34 */
 static void gr_interception(float prcp, float pet, float ci, float* hi, float* pn, float* ei) {
-    *ei = fminf(pet, prcp + (*hi) * ci);
-    *pn = fmaxf(0.f, prcp - ci * (1.f - *hi) - *ei);
+    CEN(ORC_CEN_EI_STORE, pet > prcp + (*hi) * ci);
+    *ei = orc_min(pet, prcp + (*hi) * ci);
+    *pn = orc_max(0.f, prcp - ci * (1.f - *hi) - *ei);
+    CEN(ORC_CEN_PN_INTERCEPTION, *pn > 0.f);
     *hi = *hi + (prcp - *ei - *pn) / ci;
 }
 
@@ -35,6 +58,11 @@ static void gr_production(float pn, float en, float cp, float beta, float* hp, f
     if (pn > 0.f) *pr = pn - (hp_imd - h) * cp;
     float r = hp_imd / beta;
     float r2 = r * r;
+    CEN(ORC_CEN_PN_POS, pn > 0.f);
+    CEN(ORC_CEN_EN_POS, en > 0.f);
+    CEN(ORC_CEN_TANH_SAT, pn * inv_cp > 9.f || en * inv_cp > 9.f);
+    CEN(ORC_CEN_HP_BIG, !(fabsf(hp_imd) < 15.f));
+    CEN(ORC_CEN_PERC_POW, 1.f + r2 * r2 != 1.f);
     *perc = (hp_imd * cp) * (1.f - powf(1.f + r2 * r2, -0.25f));
     *hp = hp_imd - (*perc) * inv_cp;
 }
@@ -43,7 +71,7 @@ static void gr_production(float pn, float en, float cp, float beta, float* hp, f
 static void gr_exchange(float exc, float hft, float* l) { *l = exc * powf(hft, 3.5f); }
 
 /* md_gr_operator.f90:81-110 */
-static void gr_transfer(float n, float prcp, float pr, float ct, float* ht, float* q) {
+static void gr_transfer(float n, float prcp, float pr, float ct, float* ht, float* q, int cen_floor) {
     float nm1 = n - 1.f;
     float d1pnm1 = 1.f / nm1;
     float pr_imd;
@@ -51,7 +79,9 @@ static void gr_transfer(float n, float prcp, float pr, float ct, float* ht, floa
         pr_imd = powf(powf((*ht) * ct, -nm1) - powf(ct, -nm1), -d1pnm1) - ((*ht) * ct);
     else
         pr_imd = pr;
-    float ht_imd = fmaxf(1.e-6f, *ht + pr_imd / ct);
+    CEN(ORC_CEN_GAP_PWX3_NONPOS, prcp < 0.f && powf((*ht) * ct, -nm1) - powf(ct, -nm1) <= 0.f);
+    CEN(cen_floor, !(1.e-6f < *ht + pr_imd / ct));
+    float ht_imd = orc_max(1.e-6f, *ht + pr_imd / ct);
     *ht = powf(powf(ht_imd * ct, -nm1) + powf(ct, -nm1), -d1pnm1) / ct;
     *q = (ht_imd - *ht) * ct;
 }
@@ -111,6 +141,8 @@ static void cell_step(int st, float dt, float dx, int nrow, int ncol, const int*
     float* hft = S + S_HFT * n2 + c;
     float* hst = S + S_HST * n2 + c;
     float* hlr = S + S_HLR * n2 + c;
+    CEN(ORC_CEN_CELL_STEPS, 1);
+    CEN(ORC_CEN_GAP, !(prcp >= 0.f && pet >= 0.f));
     if (st == ORC_VIC_A) {   /* vic_a_forward, md_forward_structure.f90:762-931 */
         float* husl1 = S + S_HUSL1 * n2 + c;
         float* husl2 = S + S_HUSL2 * n2 + c;
@@ -132,11 +164,17 @@ static void cell_step(int st, float dt, float dx, int nrow, int ncol, const int*
         return;
     }
     if (tape) { tape[0] = *hi; tape[1] = *hp; tape[2] = *hft; tape[3] = *hst; tape[4] = *hlr; tape[6] = prcp; tape[7] = pet; }
+    if (prcp == 0.f && pet == 0.f) {   /* the conditions under which the HIP kernels take their short "still" step */
+        int still = fabsf(*hp) < 15.f;
+        if (st == ORC_GR_B || st == ORC_GR_C) still = still && *hi >= 0.f && *hi <= 1.f;
+        CEN(ORC_CEN_STILL, still);
+        CEN(ORC_CEN_CALM_NOT_STILL, !still);
+    }
 
     if (prcp >= 0.f && pet >= 0.f) {
         if (st == ORC_GR_A || st == ORC_GR_D) {
-            ei = fminf(pet, prcp);
-            pn = fmaxf(0.f, prcp - ei);
+            ei = orc_min(pet, prcp);
+            pn = orc_max(0.f, prcp - ei);
         } else {
             gr_interception(prcp, pet, P[P_CI * n2 + c], hi, &pn, &ei);
         }
@@ -147,20 +185,22 @@ static void cell_step(int st, float dt, float dx, int nrow, int ncol, const int*
     if (st == ORC_GR_A || st == ORC_GR_B) {
         prr = 0.9f * (pr + perc) + l;
         prd = 0.1f * (pr + perc);
-        gr_transfer(5.f, prcp, prr, P[P_CFT * n2 + c], hft, &qr);
-        qd = fmaxf(0.f, prd + l);
+        gr_transfer(5.f, prcp, prr, P[P_CFT * n2 + c], hft, &qr, ORC_CEN_HFT_FLOOR);
+        qd = orc_max(0.f, prd + l);
+        CEN(ORC_CEN_QD_ZERO, !(0.f < prd + l));
         qt = (qr + qd);
     } else if (st == ORC_GR_C) {
         prr = 0.9f * 0.6f * (pr + perc) + l;
         prl = 0.9f * 0.4f * (pr + perc);
         prd = 0.1f * (pr + perc);
-        gr_transfer(5.f, prcp, prr, P[P_CFT * n2 + c], hft, &qr);
-        gr_transfer(5.f, prcp, prl, P[P_CST * n2 + c], hst, &ql);
-        qd = fmaxf(0.f, prd + l);
+        gr_transfer(5.f, prcp, prr, P[P_CFT * n2 + c], hft, &qr, ORC_CEN_HFT_FLOOR);
+        gr_transfer(5.f, prcp, prl, P[P_CST * n2 + c], hst, &ql, ORC_CEN_HST_FLOOR);
+        qd = orc_max(0.f, prd + l);
+        CEN(ORC_CEN_QD_ZERO, !(0.f < prd + l));
         qt = (qr + ql + qd);
     } else {
         prr = pr + perc;
-        gr_transfer(5.f, prcp, prr, P[P_CFT * n2 + c], hft, &qr);
+        gr_transfer(5.f, prcp, prr, P[P_CFT * n2 + c], hft, &qr, ORC_CEN_HFT_FLOOR);
         qt = qr;
     }
     if (g_qt_out) *g_qt_out = qt;
@@ -631,7 +671,10 @@ int orc_forward(const orc_config* cfg, const int* flwdir, const int* flwacc, con
     }
     float* S_imd = (float*)malloc(sizeof(float) * (size_t)(ORC_GNS * n2));
     memcpy(S_imd, S, sizeof(float) * (size_t)(ORC_GNS * n2));
+    memset(g_cen, 0, sizeof g_cen);
+    g_cen_on = 1;
     structure_forward(cfg, flwdir, flwacc, path, active, gauge_pos, prcp, pet, P, S, qsim, 0);
+    g_cen_on = 0;
     if (fstates) memcpy(fstates, S, sizeof(float) * (size_t)(ORC_GNS * n2));
     memcpy(S, S_imd, sizeof(float) * (size_t)(ORC_GNS * n2));
     free(S_imd);
@@ -865,7 +908,7 @@ static void structure_reverse(const orc_config* cfg, const int* flwdir, const in
             float ei = 0.f, pn = 0.f, en = 0.f, pr = 0.f, perc = 0.f, l = 0.f, prr, prl = 0.f, prd = 0.f;
             if (wet) {
                 float hi2 = hi, hp2 = hp;
-                if (st == ORC_GR_A || st == ORC_GR_D) { ei = fminf(pet, prcp); pn = fmaxf(0.f, prcp - ei); }
+                if (st == ORC_GR_A || st == ORC_GR_D) { ei = orc_min(pet, prcp); pn = orc_max(0.f, prcp - ei); }
                 else gr_interception(prcp, pet, P[P_CI * n2 + c], &hi2, &pn, &ei);
                 en = pet - ei;
                 gr_production(pn, en, P[P_CP * n2 + c], 1000.f, &hp2, &pr, &perc);

@@ -8,21 +8,28 @@
 
 static void vic_infiltration(float prcp, float cusl1, float cusl2, float b, float* husl1, float* husl2, float* runoff) {
     float bp1 = b + 1.f, ifl;
+    CEN(ORC_CEN_VIC_RAIN, prcp > 0.f);
     if (prcp <= 0.f) ifl = 0.f;
     else {
         float cusl = cusl1 + cusl2;
         float wusl = (*husl1) * cusl1 + (*husl2) * cusl2;
-        wusl = fmaxf(1.e-6f, wusl);
-        wusl = fminf(cusl - 1e-6f, wusl);
+        CEN(ORC_CEN_VIC_WUSL_LOW, !(1.e-6f < wusl));
+        wusl = orc_max(1.e-6f, wusl);
+        CEN(ORC_CEN_VIC_WUSL_HIGH, !(cusl - 1e-6f > wusl));
+        wusl = orc_min(cusl - 1e-6f, wusl);
         float iflm = cusl * bp1;
         float iflc = iflm * (1.f - powf(1.f - (wusl / cusl), 1.f / bp1));
+        CEN(ORC_CEN_VIC_IFL_FULL, iflc + prcp >= iflm);
         if (iflc + prcp >= iflm) ifl = cusl - wusl;
         else ifl = (cusl - wusl) - cusl * powf(1.f - ((iflc + prcp) / iflm), bp1);
-        ifl = fminf(prcp, ifl);
+        CEN(ORC_CEN_VIC_IFL_PRCP, !(prcp > ifl));
+        ifl = orc_min(prcp, ifl);
     }
-    float ifl_usl1 = fminf((1.f - *husl1) * cusl1, ifl);
+    CEN(ORC_CEN_VIC_USL1_FULL, !((1.f - *husl1) * cusl1 > ifl));
+    float ifl_usl1 = orc_min((1.f - *husl1) * cusl1, ifl);
     ifl = ifl - ifl_usl1;
-    float ifl_usl2 = fminf((1.f - *husl2) * cusl2, ifl);
+    CEN(ORC_CEN_VIC_USL2_FULL, !((1.f - *husl2) * cusl2 > ifl));
+    float ifl_usl2 = orc_min((1.f - *husl2) * cusl2, ifl);
     ifl = ifl - ifl_usl2;
     *husl1 = *husl1 + ifl_usl1 / cusl1;
     *husl2 = *husl2 + ifl_usl2 / cusl2;
@@ -34,10 +41,15 @@ static float brooks_and_corey_flow(float ks, float residual, float porosity, flo
     float flow = ks * powf((h_upper - residual) / (porosity - residual), lambda);
     float w_upper = h_upper * c_upper * porosity;
     float w_lower = h_lower * c_lower * porosity;
-    float max_flow = fminf(w_upper, c_lower - w_lower);
-    return fminf(max_flow, flow);
+    float max_flow = orc_min(w_upper, c_lower - w_lower);
+    CEN(ORC_CEN_VIC_BC_ROOM, w_upper > c_lower - w_lower);
+    CEN(ORC_CEN_VIC_BC_LIMITED, !(max_flow > flow));
+    return orc_min(max_flow, flow);
 }
-static float linear_evapotranspiration(float e, float c, float h) { return fminf(c * h, e * h); }
+static float linear_evapotranspiration(float e, float c, float h) {
+    CEN(ORC_CEN_VIC_EVAP_STORE, !(c * h > e * h));
+    return orc_min(c * h, e * h);
+}
 
 static void vic_vertical_transfer(float pet, float cusl1, float cusl2, float clsl, float ks, float* husl1, float* husl2, float* hlsl) {
     float fbc = brooks_and_corey_flow(ks, 0.f, 1.f, 1.f, cusl1, cusl2, *husl1, *husl2);
@@ -48,10 +60,12 @@ static void vic_vertical_transfer(float pet, float cusl1, float cusl2, float cls
     *hlsl = *hlsl + fbc / clsl;
     float fe = linear_evapotranspiration(pet, cusl1, *husl1);
     *husl1 = *husl1 - fe / cusl1;
-    float pet_remain = fmaxf(0.f, pet - fe);
+    CEN(ORC_CEN_VIC_PET_SPENT, !(0.f < pet - fe));
+    float pet_remain = orc_max(0.f, pet - fe);
     fe = linear_evapotranspiration(pet_remain, cusl2, *husl2);
     *husl2 = *husl2 - fe / cusl2;
-    pet_remain = fmaxf(0.f, pet_remain - fe);
+    CEN(ORC_CEN_VIC_PET_SPENT, !(0.f < pet_remain - fe));
+    pet_remain = orc_max(0.f, pet_remain - fe);
     fe = linear_evapotranspiration(pet_remain, clsl, *hlsl);
     *hlsl = *hlsl - fe / clsl;
 }
@@ -65,10 +79,12 @@ static void vic_interflow(float n, float cusl2, float* husl2, float* qi) {
 
 static void vic_baseflow(float clsl, float ds, float dsm, float ws, float* hlsl, float* qb) {
     float q;
+    CEN(ORC_CEN_VIC_ABOVE_WS, !(*hlsl <= ws));
     if (*hlsl <= ws) q = (ds * dsm) / ws * (*hlsl);
     else q = dsm * (1.f - ds / ws) * (*hlsl - ws) / (1.f - ws);
     float wlsl = clsl * (*hlsl);
-    q = fminf(wlsl, q);
+    CEN(ORC_CEN_VIC_QB_STORE, !(wlsl > q));
+    q = orc_min(wlsl, q);
     *hlsl = *hlsl - q / clsl;
     *qb = q;
 }

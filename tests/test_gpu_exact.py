@@ -49,6 +49,16 @@ def test_exact_build_is_bit_identical_at_size():
     assert r.returncode == 0 and "9 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
 
+def test_exact_build_is_bit_identical_at_the_bounds():
+    """tests/test_gpu_bounds.py under the exact-libm build: every forward and adjoint output of every case with a field on a bound of
+    the calibration box (and of the cases with states outside it), store-all and from checkpoints, BIT-IDENTICAL to the oracle."""
+    env = dict(os.environ, SMASHX_EXACT_LIBM="1")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_bounds.py"), "-q", "-m", "gpu",
+                        "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    sys.stdout.write(r.stdout[-6000:])
+    assert r.returncode == 0 and "5 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+
+
 def test_exact_build_math_layer_on_the_device():
     """tests/test_gpu_math.py under the exact-libm build: the device build of sx_libm.h (tables in LDS) bit-identical to glibc's expf /
     logf / powf over the whole float range, tanhf / expm1f on every float of +-[2^-63, 24), and every division the IEEE quotient, bit
