@@ -360,6 +360,11 @@ struct smashx_plan {
     // staging rows of the chained groups (sx_kernels.h "Staging rows"): tables of the transposition kernels, rows beyond the time blocks,
     // LDS of a wave-block's FIFOs; SMASHX_CHAIN_STAGE=0 keeps the plain rows (A/B)
     bool chain_stage = false; SxStageTables stg{}; int stg_blocks = 0, stg_rows_extra = 0; size_t stg_lds = 0;
+    // kept tape of the chained slots (DESIGN.md 4 "Kept chain tape"): hr_imd of the chained launches of the storage chunks the reverse
+    // sweep would recompute, [chunk][(time block + stage) mod Tc / 4][chained slot] float4, written in the first pass; optional, out of
+    // the reserve (SMASHX_KEEP_CHAIN_TAPE=0/1).  With it and the staging rows the chained adjoint launch of a chunk is queued before the
+    // chunk is recomputed (SMASHX_EARLY_ADJ_CHAIN=0/1)
+    float* hrk = nullptr; bool hrk_tried = false, early_adj = true;
     size_t vlds_fwd = 0, vlds_adj = 0;   // experiments only (SMASHX_DEBUG_VLDS = n or nfwd,nadj): bytes of unused dynamic LDS per vertical workgroup, which
                                      // caps the vertical workgroups resident on a compute unit (occupancy experiments)
     std::vector<hipEvent_t> buf_free;    // per pipeline sub-chunk: the R stream has finished with this part of the chunk buffers
@@ -521,6 +526,7 @@ int sublevels_env() {
 }
 
 int chunk_len(const smashx_plan* p, int c) { return std::min(p->Tc, p->nt - c * p->Tc); }
+int chain_first(const smashx_plan* p);
 
 // allocate the time-chunk buffers; Tc from cfg or from free HBM
 int ensure_chunk_buffers(smashx_plan* p, bool adjoint) {
@@ -575,6 +581,7 @@ int ensure_chunk_buffers(smashx_plan* p, bool adjoint) {
         }
         p->Tc = Tc;
         p->A.Tc = Tc;
+        p->A.hr_rows = Tc / 4;
         p->A.nx = std::max(p->sch.nxslots, 1);
         p->nchunks = (p->nt + Tc - 1) / Tc;
         {   // optional pipeline sub-chunks (V stream || R stream), equal lengths, multiples of 16.  Default: none --
@@ -599,17 +606,11 @@ int ensure_chunk_buffers(smashx_plan* p, bool adjoint) {
         int rc;
         const size_t cs = (size_t)p->npad * p->Tc;
         if (p->A.qsk) { p->dfree(p->A.qsk); p->A.qsk = nullptr; }      // (taken by a forward-only sweep before: the tapes go first)
-        {   // the hr_imd tape is written and read by the routing kernels only: its rows are shifted by the cell's stage when the
-            // extra rows (the deepest group's stages) fit beside everything else -- decided per plan, never changes results
-            const size_t extra = (size_t)p->sch.max_stage * p->npad * 4;
-            const double ntp = 3.0 + ((st == 5 || ((st == 2 || st == 3) && p->hi_tape)) ? 1.0 : (st == 2 || st == 3) ? 1.0 / SX_HIK : 0.0) + (st == 3 ? 1.0 : 0.0);
-            size_t fr = 0, tot = 0;
-            HIPCHK(hipMemGetInfo(&fr, &tot));
-            const double need = 4.0 * ((double)cs * ntp + (double)extra + (double)p->npad * (14 + (p->nchunks > 1 ? 5.0 * p->nchunks : 0.0))
-                                       + 2.0 * (double)std::max(p->ngc, 1) * p->nt) + 3.0e9;
+        {   // the hr_imd tape is written and read by the routing kernels only: its rows are shifted by the cell's stage and wrap at the
+            // rows of the chunk, so the shift costs no memory -- never changes results (SMASHX_HR_SKEW=0: the plain rows, for A/B)
             const char* e = getenv("SMASHX_HR_SKEW");
-            p->A.hr_skew = (e ? atoi(e) != 0 : true) && (double)fr > need;
-            if ((rc = p->dmalloc(&p->A.hrT, cs + (p->A.hr_skew ? extra : 0)))) return rc;
+            p->A.hr_skew = e ? atoi(e) != 0 : true;
+            if ((rc = p->dmalloc(&p->A.hrT, cs))) return rc;
         }
         if ((rc = p->dmalloc(&p->A.tape_hp, cs))) return rc;
         if ((rc = p->dmalloc(&p->A.tape_hft, cs))) return rc;
@@ -633,6 +634,25 @@ int ensure_chunk_buffers(smashx_plan* p, bool adjoint) {
         HIPCHK(hipMemGetInfo(&fr, &tot));
         if ((double)fr > (double)need + 2.0e9) { int rc; if ((rc = p->dmalloc(&p->A.qsk, need / 4))) return rc; }
     }
+    if (adjoint && !p->hrk_tried) {
+        // kept tape of the chained slots, allocated last: what the reserve still holds after the staging rows (2048^2: 16.9 GB, less
+        // than the 22.7 GB of shifted rows the routing tape no longer needs).  Untiled plans without pipeline sub-chunks only.
+        p->hrk_tried = true;
+        const int cf = chain_first(p);
+        const char* e = getenv("SMASHX_KEEP_CHAIN_TAPE");
+        const bool want = e ? atoi(e) != 0 : true;
+        if (const char* ea = getenv("SMASHX_EARLY_ADJ_CHAIN")) p->early_adj = atoi(ea) != 0;
+        if (want && p->nchunks > 1 && cf < p->sch.nrounds && !p->tiled && p->n_in == 0 && p->n_out == 0 && p->Tp >= p->Tc) {
+            const int kcs0 = p->sch.g_slot_begin[p->sch.round_group_begin[cf]], kncs = p->sch.nslots - kcs0;
+            const size_t need = (size_t)(p->nchunks - 1) * (size_t)(p->Tc / 4) * (size_t)kncs * 16;
+            size_t fr = 0, tot = 0;
+            HIPCHK(hipMemGetInfo(&fr, &tot));
+            if (kncs > 0 && (double)fr > (double)need + 2.0e9) {
+                int rc; if ((rc = p->dmalloc(&p->hrk, need / 4))) return rc;
+                p->A.kcs0 = kcs0; p->A.kncs = kncs;
+            }
+        }
+    }
     return 0;
 }
 
@@ -642,7 +662,8 @@ SxDeviceArrays view_at(const smashx_plan* p, int off) {
     B.k0 = 0; B.k1 = p->n;
     const size_t q = (size_t)(off / 4);
     B.qtT = p->A.qtT + q * p->npad * 4;
-    if (p->A.hrT) B.hrT = p->A.hrT + q * p->npad * 4;
+    B.hrk = nullptr;                     // (the chained launches of a kept chunk set it)
+    if (p->A.hrT) { if (p->A.hr_skew) B.hr_row0 = (int)q; else B.hrT = p->A.hrT + q * p->npad * 4; }
     if (p->A.qdT) B.qdT = p->A.qdT + q * p->npad * 4;
     if (!p->chain) B.qsk = nullptr;      // the launch-per-round fallback reads and writes the plain rows
     B.xT = p->A.xT + q * p->A.nx * 4;
@@ -743,10 +764,12 @@ void route_fwd_rounds(smashx_plan* p, int off, bool tape, int t0, int T, hipStre
 // the chained rounds in ONE launch (tickets: sx_kernels.h)
 // inputs_read (optional): recorded on st as soon as the pass has read the last of qtT -- after the copy into the staging rows when the
 // chained launch runs on those (it then touches no buffer of the vertical kernels), else left alone (the caller records after the pass)
-bool route_fwd_chained(smashx_plan* p, int off, bool tape, int t0, int T, hipStream_t st, hipEvent_t inputs_read = nullptr) {
+// hrk (optional): this chunk's part of the kept tape -- the launch tapes into it (whatever `tape` says)
+bool route_fwd_chained(smashx_plan* p, int off, bool tape, int t0, int T, hipStream_t st, hipEvent_t inputs_read = nullptr, float* hrk = nullptr) {
     const int nr = p->sch.nrounds, cf = chain_first(p);
     if (cf >= nr) return false;
     SxDeviceArrays B = view_at(p, off);
+    if (hrk) { B.hrk = hrk; B.hr_row0 = 0; tape = true; }
     if (!p->dom_q_active) B.qdT = nullptr;
     const size_t lds = (size_t)2 * p->M * sizeof(float4);
     const int g0 = p->sch.round_group_begin[cf], g1 = p->sch.ngroups;
@@ -763,28 +786,34 @@ bool route_fwd_chained(smashx_plan* p, int off, bool tape, int t0, int T, hipStr
     p->chain_used = true;
     return early;
 }
-// Routing launches of one pass.  Rounds below chain_first keep one launch per round (they are wide and
-// HBM-bound); the narrow, latency-bound rounds from there on run chained inside a single launch
+// Routing launches of one pass (sweep_once).  Rounds below chain_first keep one launch per round (they are wide and
+// HBM-bound: route_fwd_rounds / route_adj_rounds); the narrow, latency-bound rounds from there on run chained inside a single launch
 // (sx_kernels.h "rounds chained inside one launch"), which turns their sum into roughly the longest of them.
-bool route_fwd(smashx_plan* p, int off, bool tape, int t0, int T, hipEvent_t inputs_read = nullptr) {
-    route_fwd_rounds(p, off, tape, t0, T, p->stream_r);
-    return route_fwd_chained(p, off, tape, t0, T, p->stream_r, inputs_read);
-}
-void route_adj_chained(smashx_plan* p, int off, int t0, int T, hipStream_t st) {
+// the chained adjoint launch in two parts: the launch itself (hrk: this chunk's part of the kept tape, read in place of hrT) and the
+// copy out of the staging rows.  On staging rows the launch touches no buffer of the vertical kernels or of round 0, so it may be queued
+// long before the copy (sweep_once, "early adjoint chain")
+void route_adj_chained(smashx_plan* p, int off, int t0, int T, hipStream_t st, float* hrk = nullptr, bool launch = true, bool copy = true) {
     const int nr = p->sch.nrounds, cf = chain_first(p);
     if (cf >= nr) return;
-    const SxDeviceArrays B = view_at(p, off);
+    SxDeviceArrays B = view_at(p, off);
+    if (hrk) { B.hrk = hrk; B.hr_row0 = 0; }
     const size_t lds = (size_t)2 * p->M * sizeof(float4);
     const int g0 = p->sch.round_group_begin[cf], g1 = p->sch.ngroups;
-    reset_chain_counters(p, st);
     const int grid = g1 - g0;
-    p->mark_begin(6, st, round_cells(p, cf, nr) * T);
-    hipLaunchKernelGGL((sx_k_route_adj<true>), dim3(grid), dim3(p->M), lds, st, B, g0, g1, t0, T);
-    if (B.qsk)       // qt_b of the chained cells and the adjoint series that leave the chain: from the staging rows to where the vertical kernel,
-                     // round 0 and the exchange expect them
+    if (launch) {
+        reset_chain_counters(p, st);
+        p->mark_begin(6, st, round_cells(p, cf, nr) * T);
+        hipLaunchKernelGGL((sx_k_route_adj<true>), dim3(grid), dim3(p->M), lds, st, B, g0, g1, t0, T);
+        p->mark_end();
+        p->chain_used = true;
+    }
+    if (copy && B.qsk) {
+        // qt_b of the chained cells and the adjoint series that leave the chain: from the staging rows to where the vertical kernel,
+        // round 0 and the exchange expect them
+        p->mark_begin(7, st);
         hipLaunchKernelGGL((sx_k_chain_transpose<false>), dim3((p->stg_blocks + SX_STG_WAVES - 1) / SX_STG_WAVES), dim3(64 * SX_STG_WAVES), p->stg_lds * SX_STG_WAVES, st, B, p->stg, g0, (T + SX_BT - 1) / SX_BT, p->stg_blocks, (int)p->stg_lds);
-    p->mark_end();
-    p->chain_used = true;
+        p->mark_end();
+    }
 }
 void route_adj_rounds(smashx_plan* p, int off, int t0, int T, hipStream_t st) {
     const SxDeviceArrays B = view_at(p, off);
@@ -796,10 +825,6 @@ void route_adj_rounds(smashx_plan* p, int off, int t0, int T, hipStream_t st) {
         hipLaunchKernelGGL((sx_k_route_adj<false>), dim3(ngr), dim3(p->M), lds, st, B, g0, g0 + ngr, t0, T);
         p->mark_end();
     }
-}
-void route_adj(smashx_plan* p, int off, int t0, int T) {
-    route_adj_chained(p, off, t0, T, p->stream_r);
-    route_adj_rounds(p, off, t0, T, p->stream_r);
 }
 
 SxCostArgs cost_args(smashx_plan* p, float jobs_b) {
@@ -1610,6 +1635,12 @@ static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_o
         return 0;
     };
     static const bool early_release = []() { const char* e = getenv("SMASHX_EARLY_RELEASE"); return !(e && e[0] == '0'); }();
+    // Kept chain tape: the chained launch of the storage chunks 0 .. C - 2 tapes in the FIRST pass (where it runs under the next chunk's
+    // vertical kernel) into the plan's kept rows; their recomputation then needs neither the copy into the staging rows nor the chained
+    // launch -- round 0 is upstream of it, gauge discharge and cost are known, the chunk-end states come from the checkpoints -- and
+    // the chained adjoint launch reads the kept rows.
+    const bool keep = adjoint && C > 1 && p->hrk && !halo && chain_first(p) < p->sch.nrounds;
+    auto kept_rows = [&](int c) -> float* { return (keep && c < C - 1) ? p->hrk + (size_t)c * (size_t)(p->Tc / 4) * (size_t)p->A.kncs * 4 : nullptr; };
     auto forward_chunk = [&](int c, bool tape, bool recompute = false) -> int {
         const int t0c = c * p->Tc, Tcur = chunk_len(p, c), ns = nsub_of(Tcur);
         std::vector<hipEvent_t> ev(ns);
@@ -1636,7 +1667,9 @@ static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_o
             // storage chunk's vertical kernel (first pass of a checkpointed sweep: 3 x 3.6 ms at 2048^2); else after the whole pass.
             if ((int)p->buf_free.size() <= jb) p->buf_free.resize(jb + 1, nullptr);
             p->buf_free[jb] = p->event();
-            const bool released = route_fwd(p, off, tape, t0c + off, T, early_release ? p->buf_free[jb] : nullptr);
+            float* const hrk = kept_rows(c);
+            route_fwd_rounds(p, off, tape, t0c + off, T, sR);
+            const bool released = (hrk && recompute) ? false : route_fwd_chained(p, off, tape, t0c + off, T, sR, early_release ? p->buf_free[jb] : nullptr, hrk);
             if (halo && p->n_out > 0 && !recompute) {       // (a recomputed chunk sends nothing: every rank kept what it received)
                 halo_move(true, true, off, T, sR);
                 if ((rc = hook(1, t0c + off, T, sR))) return rc;
@@ -1710,6 +1743,7 @@ static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_o
             }
         }
         if (p->ng == 0) HIPCHK(hipMemsetAsync(p->A.qgb, 0, (size_t)std::max(p->ngc, 1) * p->nt * 4, sR));
+        bool adj_queued = false;      // the chained adjoint launch of the chunk at hand is already on the R stream
         for (int c = C - 1; c >= 0; --c) {
             const int t0c = c * p->Tc, Tcur = chunk_len(p, c);
             if (C > 1 && c < C - 1) {   // recompute this storage chunk with the tape on
@@ -1725,10 +1759,20 @@ static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_o
                     if ((rc = hook(2, t0c + off, T, sR))) return rc;  // out_buf now holds the downstream tiles' adjoint contributions
                     halo_move(false, true, off, T, sR);
                 }
-                route_adj(p, off, t0c + off, T);
+                route_adj_chained(p, off, t0c + off, T, sR, kept_rows(c), !adj_queued, true);
+                adj_queued = false;
+                route_adj_rounds(p, off, t0c + off, T, sR);
                 hipEvent_t e = p->event();
                 HIPCHK(hipEventRecord(e, sR));
                 HIPCHK(hipStreamWaitEvent(sV, e, 0));
+                // Early adjoint chain: the chained adjoint launch of the chunk below needs the kept tape, the cost seeds and the routing
+                // carry this pass has just left -- nothing its recomputation produces -- and on staging rows it writes nothing the
+                // vertical kernels or round 0 touch: queued here, it runs under this chunk's vertical adjoint and the recomputation's
+                // vertical kernel.  Its copy out of the staging rows follows round 0 of the recomputation (stream order).
+                if (jb == 0 && c > 0 && kept_rows(c - 1) && p->early_adj && p->chain && p->A.qsk) {
+                    route_adj_chained(p, 0, (c - 1) * p->Tc, chunk_len(p, c - 1), sR, kept_rows(c - 1), true, false);
+                    adj_queued = true;
+                }
                 vert_adj(p, off, t0c + off, T);
                 if (halo && p->n_in > 0) {
                     halo_move(true, false, off, T, sR);
@@ -1780,6 +1824,7 @@ static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_o
                     tm.route_fwd_chained_ms += ms; tm.route_fwd_chained_launches++; break;
             case 6: tm.route_adj_ms += ms; tm.route_adj_launches++; tm.cellsteps[2] += l.cellsteps;
                     tm.route_adj_chained_ms += ms; tm.route_adj_chained_launches++; break;
+            case 7: tm.route_adj_ms += ms; tm.route_adj_chained_ms += ms; break;      // (the copy pass of a chained adjoint launch)
             default: tm.cost_ms += ms; break;
         }
     }

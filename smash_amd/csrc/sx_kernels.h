@@ -5,8 +5,8 @@
 //   forcing      prcp/pet [nt][npad]     cell index fastest  -> lanes = consecutive cells, coalesced
 //   params/state [npad] per field
 //   qtT, hrT     [Tc/4][npad][4]         "T4": one float4 = 4 consecutive steps of one cell; cell index next.
-//                hrT belongs to the routing kernels alone; with hr_skew its row index is shifted by the cell's stage in its group:
-//                [Tc/4 + max stage][npad][4]
+//                hrT belongs to the routing kernels alone; with hr_skew its row index is shifted by the cell's stage in its group
+//                and wraps: row = (time block + stage) mod Tc/4 -- still one row per time block for every cell, no extra rows
 //                                        The marching vertical threads (lanes = consecutive cells) move
 //                                        1 KiB contiguous per wave instruction; the time-skewed routing threads
 //                                        of a group read rows tb = w - stage, and because the group's slots are
@@ -193,7 +193,11 @@ struct SxDeviceArrays {
     float *ci_b, *cp_b, *cft_b, *cst_b, *exc_b, *lr_b, *hi_b, *hp_b, *hft_b, *hst_b, *hlr_b;
     // chunk buffers
     float *qtT, *hrT;
-    int hr_skew;                  // 1: row of hrT = time block + the slot's stage (what a routing group touches in one super-step is one row)
+    int hr_skew;                  // 1: row of hrT = (time block + the slot's stage) mod hr_rows (what a routing group touches in one super-step is one row)
+    int hr_rows, hr_row0;         // rows of hrT (Tc / 4); with hr_skew, the time block of the chunk this view starts at (else hrT itself is shifted)
+    // kept tape of the chained slots (DESIGN.md "Kept chain tape"): hr_imd of ONE storage chunk, [(time block + stage) mod hr_rows][chained slot]
+    // float4, null = the chained launches use hrT.  kcs0 = first slot of the first chained group, kncs = slots of the chained groups
+    float* hrk; int kcs0, kncs;
     // tangent sweep (base_forward_d): qt_d per cell (T4 like qtT), exchange series of q_d, q_d at the gauge cells.
     // The tangents of parameters and states live in the gradient arrays (ci_b .. hlr_b) during a tangent sweep.
     float *qtdT, *xdT, *qgd;
@@ -784,10 +788,20 @@ __device__ __forceinline__ void sx_route_fwd_group(const SxDeviceArrays& A, cons
                                     : reinterpret_cast<const float4*>(TAN ? A.xdT : A.xT) + (xin >= 0 ? xin : 0);
     const size_t sstride = staged ? (size_t)A.ncs : (cell >= 0) ? (size_t)A.npad : (size_t)A.nx;
     float4* x4 = reinterpret_cast<float4*>(TAN ? A.xdT : A.xT);
-    float4* hr4 = reinterpret_cast<float4*>(A.hrT);
     // hr_imd tape, private to the routing kernels: row = time block + stage, so the slots of a group -- which work on time block
-    // w - stage in super-step w -- all write row w, cell next to cell (measured: 64 -> 8 line requests per wave store)
-    const int hs = A.hr_skew ? stage : 0;
+    // w - stage in super-step w -- all write row w, cell next to cell (measured: 64 -> 8 line requests per wave store).  The row wraps at
+    // the rows of the chunk (a slot still owns one row per time block), so it is (hr_row0 + w) mod hr_rows: the same for the whole
+    // group, kept up by the scalar unit from macro-step to macro-step.  The chained launches of a kept chunk write the same rows of the
+    // kept tape instead, slot next to slot.
+    const bool kept = CHAIN && TAPE && !TAN && A.hrk != nullptr;
+    const bool circ = A.hr_skew || kept;
+    float4* const hr4 = kept ? reinterpret_cast<float4*>(A.hrk) + (sb + j - A.kcs0) : reinterpret_cast<float4*>(A.hrT) + max(cell, 0);
+    const size_t hstride = kept ? (size_t)A.kncs : (size_t)A.npad;
+    const int hrows = A.hr_rows;
+    static_assert(SX_MU_F <= 4, "the row wrap assumes a macro-step no longer than the shortest chunk (16 steps = 4 rows)");
+    auto hwrap = [&](int r) { return r >= hrows ? r - hrows : r; };
+    auto hrow = [&](int base, int u, int tb) { return circ ? hwrap(base + u) : tb; };     // row of super-step MU * macro-step + u
+    int hrw_prev = 0, hrw = circ ? A.hr_row0 : 0;                                          // (hr_row0 + MU * macro-step) mod hr_rows
     float* gauge_out = TAN ? A.qgd : A.qg;
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     auto fetch = [&](int tb) -> float4 { return cell >= 0 ? sx_gload4s(src + (size_t)tb * sstride) : sx_gload4(src + (size_t)tb * sstride); };
@@ -798,7 +812,7 @@ __device__ __forceinline__ void sx_route_fwd_group(const SxDeviceArrays& A, cons
     for (int u = 0; u < MU; ++u) {
         const int tb = u - stage;
         nxt[u] = (valid && tb >= 0 && tb < nb) ? fetch(tb) : zero4;
-        nhr[u] = (TAN && valid && cell >= 0 && tb >= 0 && tb < nb) ? sx_gload4(hr4 + (size_t)(tb + hs) * A.npad + cell) : zero4;
+        nhr[u] = (TAN && valid && cell >= 0 && tb >= 0 && tb < nb) ? sx_gload4(hr4 + (size_t)hrow(hrw, u, tb) * hstride) : zero4;
         outq[u] = zero4; outh[u] = zero4;
     }
     const int nsuper = nb + dmax;
@@ -816,7 +830,7 @@ __device__ __forceinline__ void sx_route_fwd_group(const SxDeviceArrays& A, cons
                 const int tb = MU * (mw - 1) + u - stage;
                 if (tb >= 0 && tb < nb) {
                     if (xout >= 0) x4[(size_t)tb * A.nx + xout] = outq[u];
-                    if (TAPE) sx_gstore4s(hr4 + (size_t)(tb + hs) * A.npad + cell, outh[u]);
+                    if (TAPE) sx_gstore4s(hr4 + (size_t)hrow(hrw_prev, u, tb) * hstride, outh[u]);
                     if (A.qdT) reinterpret_cast<float4*>(A.qdT)[(size_t)tb * A.npad + cell] = outq[u];
                     if (gid >= 0) {
                         const float qv[4] = {outq[u].x, outq[u].y, outq[u].z, outq[u].w};
@@ -834,8 +848,9 @@ __device__ __forceinline__ void sx_route_fwd_group(const SxDeviceArrays& A, cons
         for (int u = 0; u < MU; ++u) {
             const int tb = MU * (mw + 1) + u - stage;
             nxt[u] = (valid && tb >= 0 && tb < nb) ? fetch(tb) : zero4;
-            if (TAN) nhr[u] = (valid && cell >= 0 && tb >= 0 && tb < nb) ? sx_gload4(hr4 + (size_t)(tb + hs) * A.npad + cell) : zero4;
+            if (TAN) nhr[u] = (valid && cell >= 0 && tb >= 0 && tb < nb) ? sx_gload4(hr4 + (size_t)hrow(hwrap(hrw + MU), u, tb) * hstride) : zero4;
         }
+        hrw_prev = hrw; hrw = hwrap(hrw + MU);
 #pragma unroll
         for (int u = 0; u < MU; ++u) {
             const int w = MU * mw + u;
@@ -998,8 +1013,17 @@ __device__ __forceinline__ void sx_route_adj_group(const SxDeviceArrays& A, cons
     const float dt = A.dt, dx = A.dx;
     const SxDiv dden = sx_mkdiv(den), ddt = sx_mkdiv(dt), dlr = sx_mkdiv((lr * lr) * 60.f);
     float4* x4 = reinterpret_cast<float4*>(A.xT);
-    const float4* hr4p = reinterpret_cast<const float4*>(A.hrT);
-    const int hs = A.hr_skew ? dmax - rstage : 0;     // the forward kernel's row shift: in reverse super-step w a group reads row nb - 1 - w + dmax
+    // the forward kernel's rows (hrT, or the kept tape of a chained launch): in reverse super-step w a group reads row
+    // (hr_row0 + nb - 1 + dmax - w) mod hr_rows
+    const bool kept = CHAIN && A.hrk != nullptr;
+    const bool circ = A.hr_skew || kept;
+    const float4* const hr4p = kept ? reinterpret_cast<const float4*>(A.hrk) + (sb + j - A.kcs0) : reinterpret_cast<const float4*>(A.hrT) + max(cell, 0);
+    const size_t hstride = kept ? (size_t)A.kncs : (size_t)A.npad;
+    const int hrows = A.hr_rows;
+    static_assert(SX_MU_A <= 4, "the row wrap assumes a macro-step no longer than the shortest chunk (16 steps = 4 rows)");
+    auto hwrap = [&](int r) { return r < 0 ? r + hrows : r; };
+    auto hrow = [&](int base, int u, int tb) { return circ ? hwrap(base - u) : tb; };
+    int hrw = circ ? (A.hr_row0 + nb - 1 + dmax) % hrows : 0;       // row of the first super-step of the macro-step requested next
     float4* qt4 = reinterpret_cast<float4*>(A.qtT);
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     const bool root_in = (cell >= 0 && par < 0 && xout >= 0);   // subtree root fed by an exchange series
@@ -1040,11 +1064,12 @@ __device__ __forceinline__ void sx_route_adj_group(const SxDeviceArrays& A, cons
         const int tbr = u - rstage;
         const int tb = nb - 1 - tbr;
         const bool ok = valid && tbr >= 0 && tbr < nb;
-        nhr[u] = (ok && cell >= 0) ? sx_gload4s(hr4p + (size_t)(tb + hs) * A.npad + cell) : zero4;
+        nhr[u] = (ok && cell >= 0) ? sx_gload4s(hr4p + (size_t)hrow(hrw, u, tb) * hstride) : zero4;
         nin[u] = (ok && root_in) ? fetch_in(tb) : zero4;
         nsd[u] = ok ? load_seed(tb) : zero4;
         outq[u] = zero4;
     }
+    hrw = hwrap(hrw - MU);
     const int nsuper = nb + dmax;
     const int nmacro = (nsuper + MU - 1) / MU;
     for (int mw = 0; mw <= nmacro; ++mw) {
@@ -1073,10 +1098,11 @@ __device__ __forceinline__ void sx_route_adj_group(const SxDeviceArrays& A, cons
             const int tbr = MU * (mw + 1) + u - rstage;
             const int tb = nb - 1 - tbr;
             const bool ok = valid && tbr >= 0 && tbr < nb;
-            nhr[u] = (ok && cell >= 0) ? sx_gload4s(hr4p + (size_t)(tb + hs) * A.npad + cell) : zero4;
+            nhr[u] = (ok && cell >= 0) ? sx_gload4s(hr4p + (size_t)hrow(hrw, u, tb) * hstride) : zero4;
             nin[u] = (ok && root_in) ? fetch_in(tb) : zero4;
             nsd[u] = ok ? load_seed(tb) : zero4;
         }
+        hrw = hwrap(hrw - MU);
 #pragma unroll
         for (int u = 0; u < MU; ++u) {
             const int w = MU * mw + u;
