@@ -8,6 +8,8 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <functional>
+#include <numeric>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -448,10 +450,11 @@ struct smashx_plan {
     struct MeanForcing {
         int state = 0;                   // 0 = not built, 1 = ready, 2 = refused (a catchment leaves the active cells)
         std::string refusal;
-        std::vector<int> begin;          // ng + 1
+        std::vector<int> count;          // ng: cells of the catchment
+        std::vector<int> begin;          // ng + 1: its list in h_list, padded with -1 to whole blocks of 64 entries
         std::vector<int> h_list;         // the lists as uploaded (smashx_prcp_indices builds its own from them)
         int *d_list = nullptr, *d_begin = nullptr;
-        SxMfState* d_state = nullptr; float *d_mp = nullptr, *d_me = nullptr;
+        float *d_state = nullptr, *d_mp = nullptr, *d_me = nullptr;
     } mf;
     // precipitation indices (smashx_prcp_indices): per gauge the catchment and the ten distance bins as one padded list, the catchment's
     // distances, the gauge constants; rebuilt when the caller's flwdst plane differs from the one they were built for
@@ -2606,9 +2609,28 @@ int smashx_multiple_run_info(const smashx_plan* p, int info[4], float* device_ms
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The set-up products on the resident forcing go in pieces, so that no launch runs for more than a fraction of a second at any grid
+// size; SMASHX_*_PIECE in the environment overrides the piece (experiments; tests force several launches with it).
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+// entries per launch: whole blocks of 64, one at least
+int piece_entries(const char* env, int preset) {
+    const char* e = getenv(env);
+    return std::max(64, e ? atoi(e) : preset) / 64 * 64;
+}
+// ev0, launch(0) .. launch(npieces - 1) with the launch error taken after each, ev1
+hipError_t launch_pieces(smashx_plan* p, long npieces, int* launches, const std::function<void(long)>& launch) {
+    hipError_t err = hipEventRecord(p->ev0, p->stream);
+    for (*launches = 0; *launches < npieces && err == hipSuccess; ++*launches) { launch(*launches); err = hipGetLastError(); }
+    return err == hipSuccess ? hipEventRecord(p->ev1, p->stream) : err;
+}
+// the device time of the SMASHX_VERBOSE lines: from ev0 to ev1
+float device_ms(smashx_plan* p) { float ms = 0.f; (void)hipEventElapsedTime(&ms, p->ev0, p->ev1); return ms; }
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------
 // adjust_interception_store (mw_interception_store.f90:19-160) on the resident forcing: kernel and mapping in sx_interception.h.
-// One pass over the period per launch; the cells go in pieces of SX_ICI_PIECE so that no launch runs for more than a fraction of a
-// second at any grid size (SMASHX_ICI_PIECE in the environment overrides the piece, for experiments).
+// One pass over the period per launch; the cells go in pieces of SX_ICI_PIECE (SMASHX_ICI_PIECE).
 // ---------------------------------------------------------------------------------------------------------
 #define SX_ICI_PIECE (1 << 19)
 int smashx_adjust_interception(smashx_plan* p, int nday, const int* day_index, float* ci) {
@@ -2631,30 +2653,23 @@ int smashx_adjust_interception(smashx_plan* p, int nday, const int* day_index, f
     int* d_day = nullptr; float* d_ci = nullptr;
     if ((rc = p->dmalloc(&d_day, (size_t)nt))) return rc;
     if ((rc = p->dmalloc(&d_ci, (size_t)p->n))) { p->dfree(d_day); return rc; }
-    const char* e = getenv("SMASHX_ICI_PIECE");
-    const int piece = std::max(64, e ? atoi(e) : SX_ICI_PIECE) / 64 * 64;
+    const int piece = piece_entries("SMASHX_ICI_PIECE", SX_ICI_PIECE);
     std::vector<float> h((size_t)p->n);
     hipStream_t sV = p->stream;
     hipError_t err = hipMemcpyAsync(d_day, day_index, (size_t)nt * sizeof(int), hipMemcpyHostToDevice, sV);
     int launches = 0;
-    if (err == hipSuccess) err = hipEventRecord(p->ev0, sV);
-    for (int k0 = 0; k0 < p->n && err == hipSuccess; k0 += piece, ++launches) {
+    if (err == hipSuccess) err = launch_pieces(p, ((long)p->n + piece - 1) / piece, &launches, [&](long i) {
         SxDeviceArrays A = p->A;
-        A.k0 = k0; A.k1 = std::min(p->n, k0 + piece);
+        A.k0 = (int)(i * piece); A.k1 = (int)std::min((long)p->n, (i + 1) * piece);
         hipLaunchKernelGGL(sx_k_adjust_interception, dim3((A.k1 - A.k0 + 63) / 64), dim3(64, rows), 0, sV, A, d_day, nc, d_ci);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipEventRecord(p->ev1, sV);
+    });
     if (err == hipSuccess) err = hipMemcpyAsync(h.data(), d_ci, (size_t)p->n * sizeof(float), hipMemcpyDeviceToHost, sV);
     if (err == hipSuccess) err = hipStreamSynchronize(sV);
     p->dfree(d_day); p->dfree(d_ci);
     if (err != hipSuccess) return fail(SMASHX_E_HIP, std::string("smashx_adjust_interception: ") + hipGetErrorString(err));
     for (int k = 0; k < p->n; ++k) ci[p->sch.cell_flat[k]] = h[k];       // the plan's own active cells; every other element keeps its value
-    if (getenv("SMASHX_VERBOSE")) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
-        fprintf(stderr, "smashx: adjust_interception %d cells x %d steps x %d candidates: %.3f ms on the device, %d launches\n", p->n, nt, nc, ms, launches);
-    }
+    if (getenv("SMASHX_VERBOSE"))
+        fprintf(stderr, "smashx: adjust_interception %d cells x %d steps x %d candidates: %.3f ms on the device, %d launches\n", p->n, nt, nc, device_ms(p), launches);
     return 0;
 }
 
@@ -2662,9 +2677,9 @@ int smashx_adjust_interception(smashx_plan* p, int nday, const int* day_index, f
 // compute_mean_forcing (mw_forcing_statistic.f90:18-75) on the resident forcing: kernel and mapping in sx_meanforcing.h.
 // mask_upstream_cells (mw_mask.f90:11-54) is restated here without recursion: from the gauge cell, every neighbour whose D8 code points
 // at a cell already taken is taken, over the whole grid; the mask read in flat order (row + col * nrow) IS the column-major order of
-// the reference's sum.  The lists are built on the first call and kept with the plan.  The list goes in pieces of SX_MF_PIECE entries
-// per launch, so that no launch runs for more than a fraction of a second at any grid size (SMASHX_MF_PIECE in the environment
-// overrides the piece: tests force several launches with it); the running sums live in a device buffer of the plan between launches.
+// the reference's sum.  The lists are built on the first call and kept with the plan, each padded with -1 to whole blocks of 64
+// entries.  A launch covers SX_MF_PIECE entries of every list (SMASHX_MF_PIECE); the running sums live in a device buffer of the plan
+// between launches.
 // ---------------------------------------------------------------------------------------------------------
 #define SX_MF_PIECE (1 << 20)
 namespace {
@@ -2675,7 +2690,7 @@ int mf_tables(smashx_plan* p) {
     const int nrow = p->cfg.nrow, ncol = p->cfg.ncol, ng = p->ng;
     const long n2 = p->n2;
     std::vector<int> list; std::vector<char> mask((size_t)n2); std::vector<long> stack;
-    M.begin.assign(1, 0);
+    M.begin.assign(1, 0); M.count.clear();
     for (int g = 0; g < ng; ++g) {
         std::fill(mask.begin(), mask.end(), 0);
         const long c0 = p->sch.cell_flat[p->sch.gauge_k[g]];
@@ -2702,7 +2717,9 @@ int mf_tables(smashx_plan* p) {
             }
             list.push_back(k);
         }
-        if (list.size() > (size_t)INT_MAX) return fail(SMASHX_E_UNSUPPORTED, "smashx_mean_forcing: the catchment lists of all gauges together exceed 2^31 entries");
+        M.count.push_back((int)list.size() - M.begin[g]);
+        while (list.size() % 64) list.push_back(-1);
+        if (list.size() > (size_t)INT_MAX - 64) return fail(SMASHX_E_UNSUPPORTED, "smashx_mean_forcing: the catchment lists of all gauges together exceed 2^31 entries");
         M.begin.push_back((int)list.size());
     }
     int rc;
@@ -2710,7 +2727,7 @@ int mf_tables(smashx_plan* p) {
     if ((rc = p->upload_vec(&M.d_begin, M.begin))) return rc;
     M.h_list = std::move(list);
     const size_t ntpad = (size_t)((p->nt + 63) / 64) * 64;
-    if ((rc = p->dmalloc(&M.d_state, (size_t)ng * ntpad))) return rc;
+    if ((rc = p->dmalloc(&M.d_state, (size_t)4 * ng * ntpad))) return rc;
     if ((rc = p->dmalloc(&M.d_mp, (size_t)ng * p->nt))) return rc;
     if ((rc = p->dmalloc(&M.d_me, (size_t)ng * p->nt))) return rc;
     M.state = 1;
@@ -2729,35 +2746,27 @@ int smashx_mean_forcing(smashx_plan* p, float* mean_prcp, float* mean_pet) {
     if ((rc = close_forcing(p))) return rc;
     auto& M = p->mf;
     const int ng = p->ng, nt = p->nt;
-    int longest = 0;
-    for (int g = 0; g < ng; ++g) longest = std::max(longest, M.begin[g + 1] - M.begin[g]);
-    const char* e = getenv("SMASHX_MF_PIECE");
-    const int piece = std::max(64, e ? atoi(e) : SX_MF_PIECE) / 64 * 64;
+    const int longest = *std::max_element(M.count.begin(), M.count.end());
+    const int nbp = piece_entries("SMASHX_MF_PIECE", SX_MF_PIECE) / 64;
     hipStream_t sV = p->stream;
-    const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_MF_WAVES);
+    const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_LW_WAVES);
     int launches = 0;
-    hipError_t err = hipEventRecord(p->ev0, sV);
-    for (long j0 = 0; j0 < longest && err == hipSuccess; j0 += piece, ++launches) {
-#define SX_MF_LAUNCH(C, P, E) hipLaunchKernelGGL((sx_k_mean_forcing<C, P, E>), grid, block, 0, sV, p->A, M.d_list, M.d_begin, ng, (int)j0, piece, M.d_state, M.d_mp, M.d_me)
+    hipError_t err = launch_pieces(p, ((longest + 63) / 64 + nbp - 1) / nbp, &launches, [&](long i) {
+#define SX_MF_LAUNCH(C, P, E) hipLaunchKernelGGL((sx_k_mean_forcing<C, P, E>), grid, block, 0, sV, p->A, M.d_list, M.d_begin, ng, (int)(i * nbp), nbp, M.d_state, M.d_mp, M.d_me)
         const bool c = p->A.prcp16 != nullptr;
         if (mean_prcp && mean_pet) { if (c) SX_MF_LAUNCH(true, true, true); else SX_MF_LAUNCH(false, true, true); }
         else if (mean_prcp) { if (c) SX_MF_LAUNCH(true, true, false); else SX_MF_LAUNCH(false, true, false); }
         else { if (c) SX_MF_LAUNCH(true, false, true); else SX_MF_LAUNCH(false, false, true); }
 #undef SX_MF_LAUNCH
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipEventRecord(p->ev1, sV);
+    });
     const size_t bytes = (size_t)ng * nt * sizeof(float);
     if (err == hipSuccess && mean_prcp) err = hipMemcpyAsync(mean_prcp, M.d_mp, bytes, hipMemcpyDeviceToHost, sV);
     if (err == hipSuccess && mean_pet) err = hipMemcpyAsync(mean_pet, M.d_me, bytes, hipMemcpyDeviceToHost, sV);
     if (err == hipSuccess) err = hipStreamSynchronize(sV);
     if (err != hipSuccess) return fail(SMASHX_E_HIP, std::string("smashx_mean_forcing: ") + hipGetErrorString(err));
-    if (getenv("SMASHX_VERBOSE")) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
+    if (getenv("SMASHX_VERBOSE"))
         fprintf(stderr, "smashx: mean_forcing %d gauges x %d steps, longest catchment %d cells, %d list entries: %.3f ms on the device, %d launches\n", ng, nt, longest,
-                M.begin[ng], ms, launches);
-    }
+                std::accumulate(M.count.begin(), M.count.end(), 0), device_ms(p), launches);
     return 0;
 }
 
@@ -2770,7 +2779,7 @@ int smashx_mean_forcing(smashx_plan* p, float* mean_prcp, float* mean_pet) {
 // (gauge_row, gauge_row), which the reference reads for pwf(1) (:181 indexes the column with the gauge's row: reproduced as written).
 // Whatever the reference would read and the plan holds no forcing for is refused.  The tables are kept with the plan and rebuilt when
 // the caller's flwdst differs from the plane they were built for.  A launch covers SX_PI_PIECE list entries of every gauge
-// (SMASHX_PI_PIECE in the environment overrides it: tests force several launches with it).
+// (SMASHX_PI_PIECE).
 // ---------------------------------------------------------------------------------------------------------
 #define SX_PI_PIECE (1 << 20)
 namespace {
@@ -2810,7 +2819,7 @@ int pi_tables(smashx_plan* p, const float* flwdst) {
         const int row = (int)(c0 % nrow);
         const float f0 = flwdst[c0];
         for (long c = 0; c < n2; ++c) d[c] = flwdst[c] - f0;
-        const int nc = M.begin[g + 1] - M.begin[g];
+        const int nc = M.count[g];
         if (nc < 2) return refuse("the catchment of gauge " + std::to_string(g) + " has " + std::to_string(nc) + " cell: the reference's quantile reads two");
         const int krr = row < ncol ? p->sch.k_of_flat[row + (long)row * nrow] : -1;
         if (krr < 0)
@@ -2886,20 +2895,17 @@ int smashx_prcp_indices(smashx_plan* p, const float* flwdst, float* prcp_indices
     const int ng = p->ng, nt = p->nt;
     int longest = 0;
     for (int g = 0; g < ng; ++g) longest = std::max(longest, Q.gauges[g].sec[SX_PI_NQ]);
-    const char* e = getenv("SMASHX_PI_PIECE");
-    const int nbp = std::max(64, e ? atoi(e) : SX_PI_PIECE) / 64;
+    const int nbp = piece_entries("SMASHX_PI_PIECE", SX_PI_PIECE) / 64;
     hipStream_t sV = p->stream;
-    const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_PI_WAVES);
+    const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_LW_WAVES);
     int launches = 0;
-    hipError_t err = hipEventRecord(p->ev0, sV);
-    for (long b0 = 0; b0 < longest && err == hipSuccess; b0 += nbp, ++launches) {
+    hipError_t err = launch_pieces(p, (longest + nbp - 1) / nbp, &launches, [&](long i) {
+        const int b0 = (int)(i * nbp);
         if (p->A.prcp16 != nullptr)
-            hipLaunchKernelGGL((sx_k_prcp_indices<true>), grid, block, 0, sV, p->A, Q.d_list, Q.d_dl, Q.d_d2l, Q.d_gauges, ng, (int)b0, nbp, Q.d_state, Q.d_out, Q.d_flag);
+            hipLaunchKernelGGL((sx_k_prcp_indices<true>), grid, block, 0, sV, p->A, Q.d_list, Q.d_dl, Q.d_d2l, Q.d_gauges, ng, b0, nbp, Q.d_state, Q.d_out, Q.d_flag);
         else
-            hipLaunchKernelGGL((sx_k_prcp_indices<false>), grid, block, 0, sV, p->A, Q.d_list, Q.d_dl, Q.d_d2l, Q.d_gauges, ng, (int)b0, nbp, Q.d_state, Q.d_out, Q.d_flag);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess) err = hipEventRecord(p->ev1, sV);
+            hipLaunchKernelGGL((sx_k_prcp_indices<false>), grid, block, 0, sV, p->A, Q.d_list, Q.d_dl, Q.d_d2l, Q.d_gauges, ng, b0, nbp, Q.d_state, Q.d_out, Q.d_flag);
+    });
     std::vector<float> h_out((size_t)4 * ng * nt); std::vector<int> h_flag((size_t)ng * nt);
     if (err == hipSuccess) err = hipMemcpyAsync(h_out.data(), Q.d_out, h_out.size() * sizeof(float), hipMemcpyDeviceToHost, sV);
     if (err == hipSuccess) err = hipMemcpyAsync(h_flag.data(), Q.d_flag, h_flag.size() * sizeof(int), hipMemcpyDeviceToHost, sV);
@@ -2911,12 +2917,9 @@ int smashx_prcp_indices(smashx_plan* p, const float* flwdst, float* prcp_indices
         memcpy(prcp_indices + o * 4, h_out.data() + o * 4, 4 * sizeof(float));
         ++written;
     }
-    if (getenv("SMASHX_VERBOSE")) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, p->ev0, p->ev1);
+    if (getenv("SMASHX_VERBOSE"))
         fprintf(stderr, "smashx: prcp_indices %d gauges x %d steps, longest list %d blocks, %ld list entries (%ld of catchments), %ld pairs written: %.3f ms on the device, %d launches\n",
-                ng, nt, longest, Q.entries, Q.catchment_entries, written, ms, launches);
-    }
+                ng, nt, longest, Q.entries, Q.catchment_entries, written, device_ms(p), launches);
     return 0;
 }
 

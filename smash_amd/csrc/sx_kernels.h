@@ -370,6 +370,12 @@ __device__ __forceinline__ unsigned sx_row_load_u16(const unsigned short* row, u
     return (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, byte_off, 0, AUX);
 }
 
+// the rain of the compact layout from its u16 count
+__device__ __forceinline__ float sx_prcp_decode(const SxDeviceArrays& A, unsigned k) {
+    const float v = (float)k * A.prcp_c;
+    return k == 65535u ? A.prcp_gap : v;
+}
+
 // Forcing cursor of one marching thread.  request() issues the loads of a step and returns at once; hold() -- called one step
 // later -- is where the wait lands (the words are pinned there, before the next request is issued), and prcp() / pet() decode the
 // held words.  Layouts: COMPACT = false: fp32 rows; true: u16 rain count + the day's PET + the hour's ratio.  The hour of day is
@@ -415,9 +421,7 @@ struct SxForcing {
     }
     __device__ __forceinline__ float prcp() const {
         if (!COMPACT) return __uint_as_float(p_w);
-        const unsigned k = (p_w >> ((kb & 4u) << 2)) & 0xffffu;     // this lane's half of the dword (kb = 4 x cell)
-        const float v = (float)k * A.prcp_c;
-        return k == 65535u ? A.prcp_gap : v;
+        return sx_prcp_decode(A, (p_w >> ((kb & 4u) << 2)) & 0xffffu);      // this lane's half of the dword (kb = 4 x cell)
     }
     __device__ __forceinline__ float pet() const {
         if (!COMPACT) return e_w;
@@ -429,9 +433,7 @@ struct SxForcing {
 __device__ __forceinline__ void sx_forcing_at(const SxDeviceArrays& A, int t, unsigned kb, float& p, float& e) {
     const size_t npad = (size_t)A.npad;
     if (A.prcp16 == nullptr) { p = sx_row_load(A.prcp + (size_t)t * npad, kb); e = sx_row_load(A.pet + (size_t)t * npad, kb); return; }
-    const unsigned raw = sx_row_load_u16(A.prcp16 + (size_t)t * npad, kb >> 1);
-    const float v = (float)raw * A.prcp_c;
-    p = raw == 65535u ? A.prcp_gap : v;
+    p = sx_prcp_decode(A, sx_row_load_u16(A.prcp16 + (size_t)t * npad, kb >> 1));
     const int q = t + A.hour0;
     const float D = sx_row_load(A.petd + (size_t)(q / 24) * npad, kb);
     e = D < 0.f ? D : D * ((sx_cfloat*)A.pet_ratio)[q % 24];

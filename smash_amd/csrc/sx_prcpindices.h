@@ -8,27 +8,20 @@
 // addition: the reference's result depends on that order, and set-up products are held to its bits.  Then, on the steps
 // with sum_p > 0 only, the closing arithmetic (sx_pi_close below) with IEEE divisions and square root in both builds.
 //
-// Same mapping as sx_meanforcing.h: one LANE carries one (gauge, step) chain, a wavefront is 64 consecutive steps of one gauge, a
-// workgroup is SX_PI_WAVES wavefronts on one such chain.  A gauge's work is ONE list of plan cells in blocks of 64 entries: section 0 is
-// the catchment, sections 1 .. 10 the ten distance bins; every section is padded to whole blocks with the entry -1, so that a block
-// belongs to one section.  A block goes through a double-buffered 64 x 64 LDS tile [step][entry] whose column is XOR-ed with the row:
-//   gather  all wavefronts, lanes across the entries, SX_PI_ROWS rows each; values formed exactly as sx_forcing_at forms the rain; no
-//           branch between the loads; a padding entry becomes -1 in the catchment (the mask drops it) and +0 in a bin (x + 0 = x for
-//           every x a sum that starts at +0 can hold)
-//   walk    wavefront 0, lane = step, along its row.  Catchment: the count and six sums, six independent dependency chains; d and d*d
-//           of the entry are wave-uniform: the walking lanes hold the block's 64 distances one per lane and read entry j's with
-//           v_readlane.  Bin: one plain sum; at the last block of a bin it is put away in the state buffer.
-// A launch covers blocks [b0, b0 + nbp) of every gauge (SX_PI_PIECE entries, smashx.hip); count, sums and the open bin sum travel
-// between launches in a device buffer of the plan, laid out [field][gauge][step].  The lane that walks a gauge's last block closes:
-// it reads its ten bin sums back, the rain of the cell (gauge_row, gauge_row) at its step -- the reference indexes the column with the
-// gauge's ROW (mw_forcing_statistic.f90:181) --, and writes (std, d1, d2, vg) and a flag; the host copies the flagged pairs only, the
-// others stay as the caller passed them.
+// A gauge's work is ONE list through sx_listwalk.h: section 0 is the catchment, sections 1 .. 10 the ten distance bins, every section
+// padded to whole blocks, so that a block belongs to one section.  A padding entry becomes -1 in the catchment (the mask drops it) and
+// +0 in a bin (x + 0 = x for every x a sum that starts at +0 can hold).  The walk:
+//   catchment  the count and six sums, six independent dependency chains; d and d*d of the entry are wave-uniform: the walking lanes
+//              hold the block's 64 distances one per lane (loaded with the block's gather) and read entry j's with v_readlane
+//   bin        one plain sum; at the last block of a bin it is put away in the state buffer
+// Carried planes: count, six sums, the open bin sum, ten finished bin sums.  The lane that walks a gauge's last block closes: it reads
+// its ten bin sums back, the rain of the cell (gauge_row, gauge_row) at its step -- the reference indexes the column with the gauge's
+// ROW (mw_forcing_statistic.f90:181) --, and writes (std, d1, d2, vg) and a flag; the host copies the flagged pairs only, the others
+// stay as the caller passed them.
 #pragma once
 
-#include "sx_kernels.h"
+#include "sx_listwalk.h"
 
-#define SX_PI_WAVES 4
-#define SX_PI_ROWS (64 / SX_PI_WAVES)
 #define SX_PI_NQ 11                         // quantiles 0, 0.1 .. 1
 #define SX_PI_NF 18                         // state fields: count, six sums, the open bin sum, ten finished bin sums
 
@@ -40,8 +33,6 @@ struct SxPiGauge {
     float cnt[SX_PI_NQ];                    // cnt[k], k = 1 .. 10: real(count(mask_k)); cnt[0] unused
     int krr;                                // plan cell of (gauge_row, gauge_row)
 };
-
-__device__ __forceinline__ int sx_pi_at(int row, int col) { return row * 64 + (col ^ row); }
 
 __device__ __forceinline__ float sx_pi_uniform(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
 
@@ -72,111 +63,78 @@ __device__ __forceinline__ void sx_pi_close(const SxPiGauge& G, int n, float sum
     res[0] = sd; res[1] = d1; res[2] = d2; res[3] = vg;
 }
 
-// grid = (ceil(nt / 64), ng), block = 64 * SX_PI_WAVES.  list: plan cells or -1; dl / d2l: d and d*d of the catchment entries;
-// state[(f * ng + g) * ntpad + t], ntpad = gridDim.x * 64; out (4, ng, nt) column-major; flag (ng, nt): 1 where out was written.
 template <bool COMPACT>
-__global__ __launch_bounds__(64 * SX_PI_WAVES, 2)
-void sx_k_prcp_indices(SxDeviceArrays A, const int* __restrict__ list, const float* __restrict__ dl, const float* __restrict__ d2l,
-                       const SxPiGauge* __restrict__ gauges, int ng, int b0, int nbp, float* __restrict__ state, float* __restrict__ out,
-                       int* __restrict__ flag) {
-    __shared__ float s_tile[2][64 * 64];                       // [buffer][step][entry]
-    const int g = blockIdx.y, t0 = blockIdx.x * 64;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const SxPiGauge& G = gauges[g];
-    const int nblk = G.sec[SX_PI_NQ];
-    if (b0 >= nblk) return;                                    // this gauge was finished by an earlier launch (uniform over the workgroup)
-    const int b1 = min(nblk, b0 + nbp);
+struct SxPiWalk {
+    const SxDeviceArrays& A; const SxPiGauge& G; const float *dl, *d2l; float *state, *out; int* flag; int ng;
     const int sec1 = G.sec[1];                                 // blocks of the catchment
-    const size_t npad = (size_t)A.npad;
-    const int r0 = wave * SX_PI_ROWS;
-
-    float vp[SX_PI_ROWS]; unsigned kp[SX_PI_ROWS]; bool in = false; float padv = 0.f;
-    float dn = 0.f, d2n = 0.f;                                 // wavefront 0: the next block's distances, lane = entry
-    auto gather = [&](int b) {
-        const int c = list[(size_t)G.lb + (size_t)b * 64 + lane];
-        in = c >= 0;
-        padv = b < sec1 ? -1.f : 0.f;
-        const size_t cell = (size_t)(in ? c : 0);
-        if (wave == 0 && b < sec1) { dn = dl[(size_t)G.db + (size_t)b * 64 + lane]; d2n = d2l[(size_t)G.db + (size_t)b * 64 + lane]; }
-#pragma unroll
-        for (int r = 0; r < SX_PI_ROWS; ++r) {
-            const int t = min(t0 + r0 + r, A.nt - 1);          // steps past the end repeat the last one and are not stored
-            if (COMPACT) kp[r] = A.prcp16[(size_t)t * npad + cell];
-            else vp[r] = A.prcp[(size_t)t * npad + cell];
-        }
-    };
-    auto put = [&](int buf) {
-#pragma unroll
-        for (int r = 0; r < SX_PI_ROWS; ++r) {
-            float p;
-            if (COMPACT) { const float v = (float)kp[r] * A.prcp_c; p = kp[r] == 65535u ? A.prcp_gap : v; }
-            else p = vp[r];
-            s_tile[buf][sx_pi_at(r0 + r, lane)] = in ? p : padv;
-        }
-    };
-
-    const int t = t0 + lane;                                   // wavefront 0: this lane's step
-    const size_t ntpad = (size_t)gridDim.x * 64;
-    auto field = [&](int f) -> float& { return state[((size_t)f * ng + g) * ntpad + (size_t)t]; };
     int n = 0; float sum_p = 0.f, sum_p2 = 0.f, sum_d = 0.f, sum_d2 = 0.f, sum_pd = 0.f, sum_pd2 = 0.f, bs = 0.f;
     int s = 0;                                                 // the section of the block being walked
-    if (wave == 0 && b0 > 0) {
+    float dn = 0.f, d2n = 0.f, dc = 0.f, d2c = 0.f;            // wavefront 0: the distances of the block loaded last and of the one in the tile, lane = entry
+    __device__ __forceinline__ float& field(int f) { return sx_lw_field(state, f, ng); }
+    __device__ __forceinline__ void resume() {
         n = __float_as_int(field(0));
         sum_p = field(1); sum_p2 = field(2); sum_d = field(3); sum_d2 = field(4); sum_pd = field(5); sum_pd2 = field(6); bs = field(7);
     }
-
-    gather(b0); put(0);
-    float dc = dn, d2c = d2n;
-    __syncthreads();
-    for (int b = b0; b < b1; ++b) {
-        const int buf = (b - b0) & 1;
-        if (b + 1 < b1) gather(b + 1);                         // in flight during the walk
-        if (wave == 0) {
-            if (b < sec1) {
-#pragma unroll
-                for (int j = 0; j < 64; ++j) {
-                    const float v = s_tile[buf][sx_pi_at(lane, j)];
-                    const float d = sx_pi_uniform(dc, j), d2 = sx_pi_uniform(d2c, j);
-                    const bool m = v >= 0.f;
-                    const float vd = __fmul_rn(v, d);
-                    n += m ? 1 : 0;
-                    sum_p = m ? __fadd_rn(sum_p, v) : sum_p;
-                    sum_p2 = m ? __fadd_rn(sum_p2, __fmul_rn(v, v)) : sum_p2;
-                    sum_d = m ? __fadd_rn(sum_d, d) : sum_d;
-                    sum_d2 = m ? __fadd_rn(sum_d2, d2) : sum_d2;
-                    sum_pd = m ? __fadd_rn(sum_pd, vd) : sum_pd;
-                    sum_pd2 = m ? __fadd_rn(sum_pd2, __fmul_rn(vd, d)) : sum_pd2;
-                }
-            } else {
-                while (b >= G.sec[s + 1]) ++s;                 // wave-uniform; empty bins are passed over
-#pragma unroll 16
-                for (int j = 0; j < 64; ++j) bs = __fadd_rn(bs, s_tile[buf][sx_pi_at(lane, j)]);
-                if (b + 1 == G.sec[s + 1]) { field(7 + s) = bs; bs = 0.f; }      // the bin is complete
-            }
-        }
-        if (b + 1 < b1) put(buf ^ 1);
-        dc = dn; d2c = d2n;
-        __syncthreads();
+    __device__ __forceinline__ float gather(int b) {
+        if (threadIdx.x < 64 && b < sec1) { const size_t i = (size_t)G.db + (size_t)b * 64 + threadIdx.x; dn = dl[i]; d2n = d2l[i]; }
+        return b < sec1 ? -1.f : 0.f;
     }
-    if (wave != 0) return;
-    if (b1 < nblk) {                                           // the list goes on in the next launch
+    __device__ __forceinline__ void stored() { dc = dn; d2c = d2n; }
+    __device__ __forceinline__ void walk(int b, const float* rain, const float*) {
+        const int lane = threadIdx.x & 63;
+        if (b < sec1) {
+#pragma unroll
+            for (int j = 0; j < 64; ++j) {
+                const float v = rain[sx_lw_at(lane, j)];
+                const float d = sx_pi_uniform(dc, j), d2 = sx_pi_uniform(d2c, j);
+                const bool m = v >= 0.f;
+                const float vd = __fmul_rn(v, d);
+                n += m ? 1 : 0;
+                sum_p = m ? __fadd_rn(sum_p, v) : sum_p;
+                sum_p2 = m ? __fadd_rn(sum_p2, __fmul_rn(v, v)) : sum_p2;
+                sum_d = m ? __fadd_rn(sum_d, d) : sum_d;
+                sum_d2 = m ? __fadd_rn(sum_d2, d2) : sum_d2;
+                sum_pd = m ? __fadd_rn(sum_pd, vd) : sum_pd;
+                sum_pd2 = m ? __fadd_rn(sum_pd2, __fmul_rn(vd, d)) : sum_pd2;
+            }
+        } else {
+            while (b >= G.sec[s + 1]) ++s;                     // wave-uniform; empty bins are passed over
+#pragma unroll 16
+            for (int j = 0; j < 64; ++j) bs = __fadd_rn(bs, rain[sx_lw_at(lane, j)]);
+            if (b + 1 == G.sec[s + 1]) { field(7 + s) = bs; bs = 0.f; }      // the bin is complete
+        }
+    }
+    __device__ __forceinline__ void put_away() {
         field(0) = __int_as_float(n);
         field(1) = sum_p; field(2) = sum_p2; field(3) = sum_d; field(4) = sum_d2; field(5) = sum_pd; field(6) = sum_pd2; field(7) = bs;
-        return;
     }
-    if (t >= A.nt) return;
-    const size_t o = (size_t)g + (size_t)t * ng;
-    if (!(sum_p > 0.f)) { flag[o] = 0; return; }               // no rain: the caller's entries stay
-    float bsum[SX_PI_NQ];
-    bsum[0] = 0.f;
+    __device__ __forceinline__ void close() {
+        const int t = blockIdx.x * 64 + (threadIdx.x & 63);
+        if (t >= A.nt) return;
+        const size_t o = (size_t)blockIdx.y + (size_t)t * ng;
+        if (!(sum_p > 0.f)) { flag[o] = 0; return; }           // no rain: the caller's entries stay
+        float bsum[SX_PI_NQ];
+        bsum[0] = 0.f;
 #pragma unroll
-    for (int k = 1; k < SX_PI_NQ; ++k) bsum[k] = G.cnt[k] == 0.f ? 0.f : field(7 + k);
-    float pcell;
-    if (COMPACT) { const unsigned raw = A.prcp16[(size_t)t * npad + (size_t)G.krr]; const float v = (float)raw * A.prcp_c; pcell = raw == 65535u ? A.prcp_gap : v; }
-    else pcell = A.prcp[(size_t)t * npad + (size_t)G.krr];
-    float res[4];
-    sx_pi_close(G, n, sum_p, sum_p2, sum_d, sum_d2, sum_pd, sum_pd2, pcell, bsum, res);
+        for (int k = 1; k < SX_PI_NQ; ++k) bsum[k] = G.cnt[k] == 0.f ? 0.f : field(7 + k);
+        const size_t i = (size_t)t * (size_t)A.npad + (size_t)G.krr;
+        const float pcell = COMPACT ? sx_prcp_decode(A, A.prcp16[i]) : A.prcp[i];
+        float res[4];
+        sx_pi_close(G, n, sum_p, sum_p2, sum_d, sum_d2, sum_pd, sum_pd2, pcell, bsum, res);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) out[o * 4 + i] = res[i];
-    flag[o] = 1;
+        for (int k = 0; k < 4; ++k) out[o * 4 + k] = res[k];
+        flag[o] = 1;
+    }
+};
+
+// grid = (ceil(nt / 64), ng), block = 64 * SX_LW_WAVES.  list: plan cells or -1; dl / d2l: d and d*d of the catchment entries;
+// state (SX_PI_NF, ng, ntpad), ntpad = gridDim.x * 64; out (4, ng, nt) column-major; flag (ng, nt): 1 where out was written.
+template <bool COMPACT>
+__global__ __launch_bounds__(64 * SX_LW_WAVES, 2)
+void sx_k_prcp_indices(SxDeviceArrays A, const int* __restrict__ list, const float* __restrict__ dl, const float* __restrict__ d2l,
+                       const SxPiGauge* __restrict__ gauges, int ng, int b0, int nbp, float* __restrict__ state, float* __restrict__ out,
+                       int* __restrict__ flag) {
+    const SxPiGauge& G = gauges[blockIdx.y];
+    SxPiWalk<COMPACT> w{A, G, dl, d2l, state, out, flag, ng};
+    sx_listwalk<COMPACT, true, false, 1>(A, list + G.lb, G.sec[SX_PI_NQ], b0, nbp, w);
 }

@@ -160,6 +160,50 @@ def step_pieces():
         assert mu.same_bits(res[False][0], res[True][0]) and mu.same_bits(res[False][1], res[True][1])
 
 
+def _forced_and_default(tag, m, nt, prcp, pet, lay, want, dt=3600.0):
+    """the default piece and SMASHX_MF_PIECE = 64 (one block per launch) against want and against each other"""
+    res = {}
+    for forced in (False, True):
+        if forced:
+            os.environ["SMASHX_MF_PIECE"] = "64"
+        else:
+            os.environ.pop("SMASHX_MF_PIECE", None)
+        s = _plan(m, nt, prcp, pet, dt=dt, layout=lay)
+        mp, me = _sentinels(m.ng, nt)
+        s.mean_forcing(mp, me)
+        info = s.forcing_info()["layout"]
+        s.close()
+        _check(f"{tag} [{info.split(':')[0]}], piece {64 if forced else 'default'}", (mp, me), want)
+        res[forced] = (mp, me)
+    os.environ.pop("SMASHX_MF_PIECE", None)
+    assert mu.same_bits(res[False][0], res[True][0]) and mu.same_bits(res[False][1], res[True][1])
+    return info
+
+
+def step_block_pieces():
+    """a launch boundary on every block boundary (SMASHX_MF_PIECE = 64): gr_c_32x32x240_d8_ragged, whose largest list is 561 cells = 9
+    blocks, the last one partly padding, over 240 steps (not a multiple of 64), against the fixture and the default piece; and an 8 x 8
+    mesh whose outlet catchment is exactly 64 cells, one full block without a padding entry, against the numpy restatement.  Compact
+    and fp32 rows; the library reports its launches on stderr (SMASHX_VERBOSE), which the test counts"""
+    from smash_amd import synth
+    os.environ["SMASHX_VERBOSE"] = "1"
+    name = "gr_c_32x32x240_d8_ragged"
+    g, prcp, pet, mp_ref, me_ref = mu.load(name)
+    sizes = [int(k.sum()) for k in mu.gauge_masks(g.mesh)]
+    assert max(sizes) == 561 and -(-max(sizes) // 64) == 9 and max(sizes) % 64 != 0 and g.nt == 240, (sizes, g.nt)
+    m = synth.make_mesh(8, 8, ng=1)
+    nt = 100
+    assert int(mu.gauge_masks(m)[0].sum()) == 64 and nt % 64 != 0
+    sp, se = synth.dense_forcing(m, nt, gap_per_million=20000)
+    assert int((sp < 0).sum()) > 0
+    want = mu.mean_forcing(m.flwdir, m.gauge_pos, sp, se)
+    for tag, lay in (("compact", _synth_layout()), ("fp32 rows", None)):
+        info = _forced_and_default(f"{name}, catchments {sizes}", g.mesh, g.nt, prcp, pet, lay, (mp_ref, me_ref), dt=g.dt)
+        assert info.startswith(tag), info
+        info = _forced_and_default("8 x 8 x 100, a catchment of 64 cells vs the numpy restatement", m, nt, sp, se, lay, want)
+        assert info.startswith(tag), info
+
+
 def step_one_output():
     """mean_pet = NULL and mean_prcp = NULL: the half that is asked for equals the full call's and is fully overwritten"""
     for name, lay in (("gr_b_16x16x96_nse_gaps__blank", _synth_layout()), ("gr_c_32x32x240_d8_ragged", None)):
@@ -256,7 +300,7 @@ def step_python():
         _check(f"{name}: compute_mean_forcing(setup, mesh, input_data)", (inp.mean_prcp, inp.mean_pet), (mp_ref, me_ref))
 
 
-STEPS = {"fixtures": step_fixtures, "cance_compact": step_cance_compact, "pieces": step_pieces, "one_output": step_one_output,
+STEPS = {"fixtures": step_fixtures, "cance_compact": step_cance_compact, "pieces": step_pieces, "block_pieces": step_block_pieces, "one_output": step_one_output,
          "refusals": step_refusals, "python": step_python}
 
 if __name__ == "__main__":

@@ -84,6 +84,32 @@ def step_pieces():
         assert pu.same_bits(res[False], res[True])
 
 
+def step_block_pieces():
+    """a launch boundary on every block boundary (SMASHX_PI_PIECE = 64), so that every section boundary and every bin-completing block
+    falls on one: gr_c_32x32x240_d8_ragged in compact and in fp32 rows against the fixture, the untouched set included, and against
+    the default piece.  The library reports its launches on stderr (SMASHX_VERBOSE), which the test compares with the blocks"""
+    os.environ["SMASHX_VERBOSE"] = "1"
+    name = "gr_c_32x32x240_d8_ragged"
+    g, prcp, flwdst, ref = pu.load(name)
+    for tag, lay in (("compact", _synth_layout()), ("fp32 rows", None)):
+        res = {}
+        for forced in (False, True):
+            if forced:
+                os.environ["SMASHX_PI_PIECE"] = "64"
+            else:
+                os.environ.pop("SMASHX_PI_PIECE", None)
+            s = _plan(g.mesh, g.nt, prcp, g.pet, dt=g.dt, layout=lay)
+            info = s.forcing_info()["layout"]
+            assert info.startswith(tag), info
+            out = pu.sentinels(g.mesh.ng, g.nt)
+            s.prcp_indices(flwdst, out)
+            s.close()
+            _check(f"{name} [{tag}], piece {64 if forced else 'default'}", out, ref)
+            res[forced] = out
+        os.environ.pop("SMASHX_PI_PIECE", None)
+        assert pu.same_bits(res[False], res[True])
+
+
 def step_second_plane():
     """a second call with another flwdst gives that plane's result, the first plane again the first result; smashx_mean_forcing
     before, between and after stays bit-equal to its fixture"""
@@ -212,7 +238,7 @@ def step_python():
             assert a.shape == (g.mesh.ng, g.nt) and a.dtype == F and pu.same_bits(a, want)
 
 
-STEPS = {"fixtures": step_fixtures, "pieces": step_pieces, "second_plane": step_second_plane, "refusals": step_refusals, "python": step_python}
+STEPS = {"fixtures": step_fixtures, "pieces": step_pieces, "block_pieces": step_block_pieces, "second_plane": step_second_plane, "refusals": step_refusals, "python": step_python}
 
 if __name__ == "__main__":
     import torch  # noqa: F401  (its HIP runtime must initialise before libsmashx's: tests/conftest.py)

@@ -23,7 +23,7 @@ LIMIT = 300
 BUILDS = {"default": "0", "exact": "1"}
 
 
-def _step(step, build):
+def _step(step, build, with_stderr=False):
     env = dict(os.environ, SMASHX_EXACT_LIBM=BUILDS[build])
     env.pop("SMASHX_MF_PIECE", None)
     r = subprocess.run([sys.executable, os.path.join(HERE, "mean_forcing_worker.py"), step], env=env, capture_output=True, text=True,
@@ -31,7 +31,7 @@ def _step(step, build):
     print(r.stdout)
     assert r.returncode == 0, f"step {step} ({build} build) failed with status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     assert f"OK {step} {'exact-libm' if build == 'exact' else 'default'} build" in r.stdout
-    return r.stdout
+    return (r.stdout, r.stderr) if with_stderr else r.stdout
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))
@@ -54,6 +54,17 @@ def test_list_in_pieces_over_several_launches(build):
     """96 x 96 x 200 with gaps, a 9216-cell list and two nested ones: SMASHX_MF_PIECE = 2048 (5 launches, the running sums carried on the
     device) equals the restatement and the default piece, in the compact layout and in fp32 rows"""
     _step("pieces", build)
+
+
+@pytest.mark.parametrize("build", sorted(BUILDS))
+def test_one_block_per_launch(build):
+    """SMASHX_MF_PIECE = 64 puts a launch boundary on every block boundary: the ragged fixture (561 cells = 9 blocks, the last partly
+    padding, 240 steps) equals the fixture and the default piece; a 64-cell catchment (one full block, no padding entry) equals the
+    restatement; compact and fp32 rows.  Per layout the library reports 1, 9, 1 and 1 launches"""
+    out, err = _step("block_pieces", build, with_stderr=True)
+    assert out.count("0 + 0 differ from the reference, 0 + 0 kept the sentinel") == 8
+    launches = [int(l.rsplit(",", 1)[1].split()[0]) for l in err.splitlines() if l.startswith("smashx: mean_forcing ")]
+    assert launches == [1, 9, 1, 1] * 2, launches
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))

@@ -23,7 +23,7 @@ LIMIT = 300
 BUILDS = {"default": "0", "exact": "1"}
 
 
-def _step(step, build):
+def _step(step, build, with_stderr=False):
     env = dict(os.environ, SMASHX_EXACT_LIBM=BUILDS[build])
     env.pop("SMASHX_PI_PIECE", None)
     env.pop("SMASHX_MF_PIECE", None)
@@ -32,7 +32,7 @@ def _step(step, build):
     print(r.stdout)
     assert r.returncode == 0, f"step {step} ({build} build) failed with status {r.returncode}\n{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
     assert f"OK {step} {'exact-libm' if build == 'exact' else 'default'} build" in r.stdout
-    return r.stdout
+    return (r.stdout, r.stderr) if with_stderr else r.stdout
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))
@@ -48,6 +48,18 @@ def test_lists_in_pieces_over_several_launches(build):
     """96 x 96 x 200 with gaps, the outlet's catchment plus its bins and two nested gauges: SMASHX_PI_PIECE = 4096 (5 launches, the
     sums carried on the device) equals the restatement and the default piece, in the compact layout and in fp32 rows"""
     _step("pieces", build)
+
+
+@pytest.mark.parametrize("build", sorted(BUILDS))
+def test_one_block_per_launch(build):
+    """SMASHX_PI_PIECE = 64 puts a launch boundary on every block boundary, section boundaries and bin-completing blocks included: the
+    ragged fixture equals the fixture, untouched set included, and the default piece, in the compact layout and in fp32 rows; the
+    forced calls take one launch per block of the longest list, the others one"""
+    import re
+    out, err = _step("block_pieces", build, with_stderr=True)
+    assert out.count("(the same set: True)") == 4 and out.count(", 0 entries differ from the reference") == 4
+    runs = [(int(a), int(b)) for a, b in re.findall(r"smashx: prcp_indices .*?longest list (\d+) blocks.*?, (\d+) launches", err)]
+    assert len(runs) == 4 and runs[0][0] > 9 and [b for _, b in runs] == [1, runs[0][0]] * 2, runs
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))

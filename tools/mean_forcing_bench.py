@@ -15,75 +15,34 @@ and the kernel's registers, waves per SIMD and LDS (a listing written by tools/k
 import argparse
 import json
 import os
-import re
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from interception_bench import CapturedStderr      # noqa: E402
+from resident_forcing import CapturedStderr, plan_with_device_forcing, timed      # noqa: E402
 
 CHAIN_CYCLES_PER_CELL = 4.0      # a dependent VALU instruction of one wavefront: 64 lanes over a 16-wide SIMD
 CLOCK_GHZ = 2.4
 
 
 def one_size(n, nt, ng, reps, torch, dev, hbm_TBps):
-    import bench
-    import smash_amd
-    from smash_amd import synth
-    from smash_amd.solver import Solver
-    t_setup = time.perf_counter()
-    m = synth.make_mesh(n, n, ng=ng)
-    setup = smash_amd.SetupDT(0, ng, structure="gr-b", dt=3600.0, ntime_step=nt)
-    mesh = smash_amd.MeshDT.from_synth(setup, m)
-    sol = Solver(setup, mesh)
-    sol.set_forcing_layout(compact=True, prcp_factor=0.1, pet_ratio=synth._pet_tables()[1], pet_hour0=0)
-    rows, cols = sol.cell_order()
-    d_rows = torch.from_numpy(rows.astype(np.int64)).to(dev)
-    d_cols = torch.from_numpy(cols.astype(np.int64)).to(dev)
-    tb = max(24, (1 << 26) // max(sol.ncells, 1) // 24 * 24)
-    for t0 in range(0, nt, tb):
-        t1 = min(nt, t0 + tb)
-        prcp, pet = bench.forcing_block(d_rows, d_cols, t0, t1, dev)
-        torch.cuda.synchronize()
-        sol.set_forcing_device_block(t0, t1, prcp.data_ptr(), pet.data_ptr())
-        del prcp, pet
-    del d_rows, d_cols
-    torch.cuda.empty_cache()
-    info = sol.forcing_info()
-    setup_s = time.perf_counter() - t_setup
+    m, _, sol, info, setup_s = plan_with_device_forcing(n, nt, ng, torch, dev)
     catch = [int(m.flwacc[r, c]) for r, c in np.asarray(m.gauge_pos).reshape(-1, 2)]     # cells upstream of a gauge, itself included
     mp = np.zeros((ng, nt), np.float32, order="F")
     me = np.zeros((ng, nt), np.float32, order="F")
-    wall, device, launches = [], [], 0
-    for rep in range(reps + 1):                                # the first call is a warm-up (code object load, catchment lists)
-        with CapturedStderr() as cap:
-            t0 = time.perf_counter()
-            sol.mean_forcing(mp, me)
-            w = time.perf_counter() - t0
-        mt = re.search(r"mean_forcing .*?: ([0-9.]+) ms on the device, (\d+) launches", cap.text)
-        if mt is None:
-            raise SystemExit("the library did not report its device time (SMASHX_VERBOSE): " + cap.text[-500:])
-        if rep == 0:
-            first_wall = w
-        else:
-            wall.append(w); device.append(float(mt.group(1)) * 1e-3); launches = int(mt.group(2))
+    t, _ = timed(lambda: sol.mean_forcing(mp, me), r"mean_forcing .*?: (?P<ms>[0-9.]+) ms on the device, (?P<launches>\d+) launches", reps)
     cells = sol.ncells
     sol.close()
-    wall_s, dev_s = statistics.median(wall), statistics.median(device)
+    dev_s = t["device_s_median"]
     bpc = info["resident_bytes_per_cellstep"]
     gathered = float(sum(catch)) * nt * bpc
     once = float(cells) * nt * bpc
     chain_s = max(catch) * CHAIN_CYCLES_PER_CELL / (CLOCK_GHZ * 1e9)
     return {"grid": f"{n}x{n}", "cells": cells, "nt": nt, "gauges": ng, "catchment_cells": catch, "forcing": info, "setup_s": round(setup_s, 2),
-            "reps": reps, "first_call_wall_s": round(first_wall, 4), "wall_s_median": round(wall_s, 4), "wall_s_all": [round(v, 4) for v in wall],
-            "device_s_median": round(dev_s, 4), "device_s_all": [round(v, 4) for v in device], "launches": launches,
-            "device_s_per_launch": round(dev_s / launches, 4), "wavefronts_of_steps": ng * ((nt + 63) // 64),
+            "reps": reps, **t, "device_s_per_launch": round(dev_s / t["launches"], 4), "wavefronts_of_steps": ng * ((nt + 63) // 64),
             "masked_cellsteps_per_s_device": float(sum(catch)) * nt / dev_s,
             "ns_per_cell_of_the_longest_list": round(dev_s / max(catch) * 1e9, 2),
             "floor_bytes_s": {"every_gauge_reads_its_cells": round(gathered / (hbm_TBps * 1e12), 4), "every_cell_once": round(once / (hbm_TBps * 1e12), 4)},

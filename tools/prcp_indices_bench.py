@@ -13,69 +13,23 @@ stderr is captured), median of --reps after one warm-up, the ratio of the two pa
 import argparse
 import json
 import os
-import re
-import statistics
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-from interception_bench import CapturedStderr      # noqa: E402
+from resident_forcing import CapturedStderr, plan_with_device_forcing, timed      # noqa: E402
 
 CHAIN_CYCLES_PER_CELL = 4.0      # a dependent VALU instruction of one wavefront: 64 lanes over a 16-wide SIMD
 CLOCK_GHZ = 2.4
 RAIN_BYTES = 2.0                 # the compact layout holds the rain as one u16 per cell-step
 
 
-def timed(call, pattern, reps):
-    wall, device, last = [], [], None
-    for rep in range(reps + 1):                                # the first call is a warm-up (code object load, lists built and uploaded)
-        with CapturedStderr() as cap:
-            t0 = time.perf_counter()
-            call()
-            w = time.perf_counter() - t0
-        mt = re.search(pattern, cap.text)
-        if mt is None:
-            raise SystemExit("the library did not report its device time (SMASHX_VERBOSE): " + cap.text[-500:])
-        if rep == 0:
-            first = w
-        else:
-            wall.append(w); device.append(float(mt.group("ms")) * 1e-3); last = mt
-    return {"first_call_wall_s": round(first, 4), "wall_s_median": round(statistics.median(wall), 4), "wall_s_all": [round(v, 4) for v in wall],
-            "device_s_median": round(statistics.median(device), 4), "device_s_all": [round(v, 4) for v in device],
-            "launches": int(last.group("launches"))}, last
-
-
 def one_size(n, nt, ng, reps, torch, dev, hbm_TBps):
-    import bench
-    import smash_amd
-    from smash_amd import synth
-    from smash_amd.solver import Solver
-    t_setup = time.perf_counter()
-    m = synth.make_mesh(n, n, ng=ng)
-    setup = smash_amd.SetupDT(0, ng, structure="gr-b", dt=3600.0, ntime_step=nt)
-    mesh = smash_amd.MeshDT.from_synth(setup, m)
+    m, mesh, sol, info, setup_s = plan_with_device_forcing(n, nt, ng, torch, dev)
     flwdst = mesh.flwdst
-    sol = Solver(setup, mesh)
-    sol.set_forcing_layout(compact=True, prcp_factor=0.1, pet_ratio=synth._pet_tables()[1], pet_hour0=0)
-    rows, cols = sol.cell_order()
-    d_rows = torch.from_numpy(rows.astype(np.int64)).to(dev)
-    d_cols = torch.from_numpy(cols.astype(np.int64)).to(dev)
-    tb = max(24, (1 << 26) // max(sol.ncells, 1) // 24 * 24)
-    for t0 in range(0, nt, tb):
-        t1 = min(nt, t0 + tb)
-        prcp, pet = bench.forcing_block(d_rows, d_cols, t0, t1, dev)
-        torch.cuda.synchronize()
-        sol.set_forcing_device_block(t0, t1, prcp.data_ptr(), pet.data_ptr())
-        del prcp, pet
-    del d_rows, d_cols
-    torch.cuda.empty_cache()
-    info = sol.forcing_info()
-    setup_s = time.perf_counter() - t_setup
     catch = [int(m.flwacc[r, c]) for r, c in np.asarray(m.gauge_pos).reshape(-1, 2)]
     mp = np.zeros((ng, nt), np.float32, order="F")
     out = np.full((4, ng, nt), -1.0, np.float32, order="F")
