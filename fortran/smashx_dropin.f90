@@ -95,6 +95,11 @@ module smashx_c
             type(smashx_options), intent(in) :: opt
             integer(c_int) :: rc
         end function
+        function smashx_set_signature_inputs(plan, mean_prcp, mask_event) bind(C, name="smashx_set_signature_inputs") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: plan, mean_prcp, mask_event
+            integer(c_int) :: rc
+        end function smashx_set_signature_inputs
         function smashx_abi_sizes(sizes) bind(C, name="smashx_abi_sizes") result(ver)
             import
             integer(c_int) :: sizes(7)
@@ -242,7 +247,17 @@ contains
         case ("se"); id = 4
         case ("rmse"); id = 5
         case ("logarithmic"); id = 6
-        case default; id = 99     !  signatures: rejected by smashx_set_options
+        !  the signatures (mwd_cost.f90:125-129): they read input_data%mean_prcp and setup%optimize%mask_event, handed over in
+        !  smashx_prepare
+        case ("Crc"); id = 7
+        case ("Cfp2"); id = 8
+        case ("Cfp10"); id = 9
+        case ("Cfp50"); id = 10
+        case ("Cfp90"); id = 11
+        case ("Epf"); id = 12
+        case ("Elt"); id = 13
+        case ("Erc"); id = 14
+        case default; id = 99     !  unknown: rejected by smashx_set_options
         end select
     end function sx_jobs_id
 
@@ -443,6 +458,15 @@ subroutine smashx_prepare(setup, mesh, input_data, plain)
             opt%denormalize_forward = 0
             opt%njr = 0
         end if
+    end if
+    !  a signature criterion: the catchment-mean rain and the event mask go over before the options, which decide on them what the
+    !  library refuses (include/smashx_signature.h).  mean_prcp is allocated only under setup%mean_forcing: without it the library
+    !  is handed a null pointer and says so.
+    if (mesh%ng .gt. 0 .and. any(opt%jobs_fun(1:min(setup%optimize%njf, 8)) .ge. 7 .and. &
+    &   opt%jobs_fun(1:min(setup%optimize%njf, 8)) .le. 14)) then
+        fkey = c_null_ptr
+        if (allocated(input_data%mean_prcp)) fkey = c_loc(input_data%mean_prcp)
+        call sx_check(smashx_set_signature_inputs(sx_plan, fkey, c_loc(setup%optimize%mask_event)), "set_signature_inputs")
     end if
     call sx_check(smashx_set_options(sx_plan, opt), "set_options")
 

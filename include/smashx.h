@@ -29,7 +29,10 @@ extern "C" {
 #define SMASHX_GNS 8  /* md_constant.f90:33  hi hp hft hst husl1 husl2 hlsl hlr */
 
 enum { SMASHX_GR_A = 1, SMASHX_GR_B = 2, SMASHX_GR_C = 3, SMASHX_GR_D = 4, SMASHX_VIC_A = 5 };   /* setup%structure, forward.f90:43-65 */
-enum { SMASHX_NSE = 1, SMASHX_KGE = 2, SMASHX_KGE2 = 3, SMASHX_SE = 4, SMASHX_RMSE = 5, SMASHX_LOGARITHMIC = 6 }; /* mwd_cost.f90:98-126 */
+enum { SMASHX_NSE = 1, SMASHX_KGE = 2, SMASHX_KGE2 = 3, SMASHX_SE = 4, SMASHX_RMSE = 5, SMASHX_LOGARITHMIC = 6, /* mwd_cost.f90:98-126 */
+       /* the hydrological signatures (mwd_cost.f90:125-129, 772-970): they read mean_prcp and mask_event, smashx_signature.h */
+       SMASHX_CRC = 7, SMASHX_CFP2 = 8, SMASHX_CFP10 = 9, SMASHX_CFP50 = 10, SMASHX_CFP90 = 11, SMASHX_EPF = 12, SMASHX_ELT = 13,
+       SMASHX_ERC = 14 };
 enum { SMASHX_PRIOR = 1, SMASHX_SMOOTHING = 2, SMASHX_HARD_SMOOTHING = 3 };   /* mwd_cost.f90:199-224 */
 enum { SMASHX_P_CI = 0, SMASHX_P_CP = 1, SMASHX_P_BETA = 2, SMASHX_P_CFT = 3, SMASHX_P_CST = 4, SMASHX_P_ALPHA = 5,
        SMASHX_P_EXC = 6, SMASHX_P_B = 7, SMASHX_P_CUSL1 = 8, SMASHX_P_CUSL2 = 9, SMASHX_P_CLSL = 10, SMASHX_P_KS = 11,
@@ -427,6 +430,8 @@ int smashx_lbfgsb_destroy(smashx_lbfgsb* opt);
 #include "smashx_forcing.h"
 /* ---- precipitation indices of the resident forcing: declared in smashx_prcp.h, likewise ------------------------------------------------ */
 #include "smashx_prcp.h"
+/* ---- inputs of the signature-based criteria: declared in smashx_signature.h, likewise ---------------------------------------------------- */
+#include "smashx_signature.h"
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """ctypes view of include/smashx.h, declared once: the header's constants, one class per struct (STRUCTS), one prototype per function
-(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h and PRCP_PROTOTYPES for include/smashx_prcp.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
+(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h, PRCP_PROTOTYPES for include/smashx_prcp.h and SIGNATURE_PROTOTYPES for include/smashx_signature.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
 PROTOTYPES.  Loading fails loudly when libsmashx.so is missing: there is no Python / CPU implementation of the solver behind this
 module."""
 from __future__ import annotations
@@ -18,7 +18,9 @@ ABI_VERSION = 9
 GNP, GNS = 16, 8
 E_OK, E_ARG, E_UNSUPPORTED, E_HIP, E_NODEVICE, E_MESH, E_STATE = 0, -1, -2, -3, -4, -5, -6
 STRUCTURES = {"gr-a": 1, "gr-b": 2, "gr-c": 3, "gr-d": 4, "vic-a": 5}                       # SMASHX_GR_A ...
-JOBS_FUN = {"nse": 1, "kge": 2, "kge2": 3, "se": 4, "rmse": 5, "logarithmic": 6}             # SMASHX_NSE ...
+JOBS_FUN = {"nse": 1, "kge": 2, "kge2": 3, "se": 4, "rmse": 5, "logarithmic": 6,              # SMASHX_NSE ...
+            "Crc": 7, "Cfp2": 8, "Cfp10": 9, "Cfp50": 10, "Cfp90": 11, "Epf": 12, "Elt": 13, "Erc": 14}   # SMASHX_CRC ... (the signatures)
+SIGNATURE_FUN = ("Crc", "Cfp2", "Cfp10", "Cfp50", "Cfp90", "Epf", "Elt", "Erc")                 # read mean_prcp (and, E*, mask_event)
 JREG_FUN = {"prior": 1, "smoothing": 2, "hard_smoothing": 3}                                  # SMASHX_PRIOR ...
 HYPER = {"hyper-linear": 1, "hyper-polynomial": 2}                                            # SMASHX_HYPER_LINEAR ...
 LBFGSB_START, LBFGSB_FG, LBFGSB_NEW_X, LBFGSB_CONVERGED, LBFGSB_ABNORMAL = range(5)
@@ -172,6 +174,13 @@ PRCP_PROTOTYPES = {
     "smashx_prcp_indices": (_int, [ptr, ptr, ptr]),
 }
 PRCP_SYMBOLS = list(PRCP_PROTOTYPES)
+# ---- every function of include/smashx_signature.h (inputs of the signature-based criteria, which smashx.h includes as well), the same
+# way; tests/test_signature_cost_cpu.py reads that header and compares
+SIGNATURE_PROTOTYPES = {
+    "smashx_set_signature_inputs": (_int, [ptr, ptr, ptr]),
+    "smashx_jobs_of_qsim": (_int, [ptr, ptr, _float, ptr, ptr, ptr, ptr]),
+}
+SIGNATURE_SYMBOLS = list(SIGNATURE_PROTOTYPES)
 
 
 class SmashxError(RuntimeError):
@@ -192,7 +201,7 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: build the HIP library first (__graft_entry__.build()); "
                               "smash_amd has no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()) + list(SIGNATURE_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         # the structs above mirror include/smashx.h by hand: refuse a library built from another layout (a stale .so would have

@@ -417,6 +417,18 @@ struct smashx_plan {
     int med_nslots = 0; int* d_med_slot = nullptr; float* d_medx = nullptr; int* d_medx_idx = nullptr;   // ... of several tiles
     smashx_reduce_fn med_fn = nullptr; void* med_user = nullptr; std::vector<int> med_slot_h;
     float jobs = 0.f;
+    // signature criteria (smashx_set_signature_inputs, sx_signature.h): host copies of what decides the refusals of smashx_set_options
+    // ([g][t]), the device tables, and whether they belong to the qobs / inputs / options the plan holds now
+    struct Signature {
+        bool have = false, have_mask = false, ready = false;
+        std::vector<float> h_po; std::vector<int> h_mask;
+        int maxev_cap = -1;
+        int obs_s0 = -1, obs_lds = -1;   // the start step and buffers den_obs / n_obs on the device were formed with; -1: none
+        SxSigArgs a{};
+        float* d_po = nullptr; int *d_nev = nullptr, *d_ev = nullptr;
+        float *d_probe_b = nullptr, *d_probe_gb = nullptr, *d_probe_gd = nullptr, *d_probe_keep = nullptr;     // smashx_jobs_of_qsim
+    } sig;
+    std::vector<float> h_qobs;       // [g][t], kept for the same purpose
     // optional whole-domain outputs of forward sweeps (host arrays owned by the caller)
     float* h_qsim_domain = nullptr; float* h_net_prcp_domain = nullptr; int dom_sparse = 0;
     bool dom_q_active = false;       // the running sweep stores every cell's discharge (forward sweeps only)
@@ -841,14 +853,31 @@ SxCostArgs cost_args(smashx_plan* p, float jobs_b) {
     C.med = p->d_med; C.med_idx = p->d_med_idx;
     C.nslots = p->med_nslots; C.slot = p->d_med_slot; C.medx = p->d_medx; C.medx_idx = p->d_medx_idx;
     C.jobs_b = jobs_b;
+    C.sig = p->sig.a;
     return C;
 }
 
-int run_cost(smashx_plan* p, int adjoint, float cost_b) {
+bool is_signature(int fun) { return fun >= SMASHX_CRC && fun <= SMASHX_ERC; }
+bool wants_signature(const smashx_options& o) {
+    for (int j = 0; j < o.njf; ++j) if (is_signature(o.jobs_fun[j])) return true;
+    return false;
+}
+// checked where a sweep ENTERS (smashx_sweep, smashx_forward_d, smashx_jobs_of_qsim), before anything is launched
+int signature_state(smashx_plan* p) {
+    if (wants_signature(p->opt) && p->ng > 0 && !p->sig.ready)
+        return fail(SMASHX_E_STATE, "signature criteria: qobs or the signature inputs changed, or the options were refused, after the last accepted smashx_set_options; set the options again");
+    return 0;
+}
+
+int run_cost(smashx_plan* p, int adjoint, float cost_b, float* qsim_b = nullptr, float* qgb = nullptr) {
     if (p->ng == 0 && p->med_nslots == 0) return 0;      // (a tile without gauges still takes part in the sum of the median's slots)
     SxCostArgs C = cost_args(p, cost_b);
+    if (qsim_b) { C.qsim_b = qsim_b; C.qgb = qgb; }      // smashx_jobs_of_qsim: seeds into buffers of its own
     p->mark_begin(4, p->stream_r);
     if (p->ng > 0) hipLaunchKernelGGL(sx_k_cost_sums, dim3(p->ng), dim3(64), 0, p->stream_r, C);
+    if (p->ng > 0 && (C.sig.want & (SX_SIG_WANT_CRC | SX_SIG_WANT_EVENTS))) hipLaunchKernelGGL(sx_k_sig_sums, dim3(p->ng), dim3(64), 0, p->stream_r, C);
+    if (p->ng > 0 && (C.sig.want & SX_SIG_WANT_PCT))
+        hipLaunchKernelGGL(sx_k_sig_pct, dim3(p->ng), dim3(SX_SIG_PCT_THREADS), C.sig.lds ? (size_t)(p->nt - C.s0) * 8 : 0, p->stream_r, C);
     if (p->med_nslots > 0) {
         // the median spans several tiles: local gauge_jobs into their slots, slots summed over the ranks, then the median of all
         HIPCHK(hipMemsetAsync(p->d_medx, 0, (size_t)p->med_nslots * sizeof(float), p->stream_r));
@@ -1333,6 +1362,211 @@ int smashx_set_qobs(smashx_plan* p, const float* qobs) {
         for (int t = 0; t < p->nt; ++t) tr[(size_t)g * p->nt + t] = qobs[g + (size_t)p->ng * t];   // (ng,nt) column-major -> [g][t]
     HIPCHK(hipMemcpy(p->d_qobs, tr.data(), tr.size() * 4, hipMemcpyHostToDevice));
     p->have_qobs = true;
+    if (tr != p->h_qobs) {          // (the drop-ins hand the same observations over before every call: nothing of the criteria's is redone then)
+        p->h_qobs.swap(tr);
+        p->sig.ready = false; p->sig.obs_s0 = -1;
+    }
+    return 0;
+}
+
+namespace {
+// The signature criteria of options o on the plan's qobs and signature inputs (include/smashx_signature.h): refuses what the reference
+// would compute from an unassigned num / den, builds the event tables of the slice that starts at optimize_start_step, and forms the
+// quantiles of the observed series on the device.  Touches nothing of the plan but p->sig.
+int prepare_signature(smashx_plan* p, const smashx_options* o, const std::vector<float>& wgauge) {
+    auto& G = p->sig;
+    G.a.want = 0; G.ready = false;
+    bool crc = false, ev = false, erc = false, pct = false;
+    for (int j = 0; j < o->njf; ++j) {
+        const int f = o->jobs_fun[j];
+        crc |= f == SMASHX_CRC; erc |= f == SMASHX_ERC; pct |= f >= SMASHX_CFP2 && f <= SMASHX_CFP90;
+        ev |= f == SMASHX_EPF || f == SMASHX_ELT || f == SMASHX_ERC;
+    }
+    if (!(crc || ev || pct) || p->ng == 0) return 0;
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "signature-based jobs_fun on a tiled plan (tile / owner_mask)");
+    if (!G.have) return fail(SMASHX_E_UNSUPPORTED, "signature-based jobs_fun read mean_prcp: call smashx_set_signature_inputs first");
+    if (ev && !G.have_mask) return fail(SMASHX_E_UNSUPPORTED, "Epf / Elt / Erc read mask_event: smashx_set_signature_inputs was given none");
+    if (!p->have_qobs) return fail(SMASHX_E_STATE, "signature-based jobs_fun: set qobs before the options");
+    const int nt = p->nt, ng = p->ng, s0 = o->optimize_start_step - 1;
+    std::vector<int> flw(ng);
+    HIPCHK(hipMemcpy(flw.data(), p->d_gauge_flwacc, (size_t)ng * 4, hipMemcpyDeviceToHost));
+    std::vector<int> nev(ng, 0);
+    std::vector<std::vector<int>> evs(ng);
+    int maxev = 0;
+    for (int g = 0; g < ng; ++g) {
+        const float* po = &G.h_po[(size_t)g * nt];
+        std::vector<char> valid(nt, 0);             // qo >= 0 and po >= 0 (mwd_cost.f90:847, 927)
+        bool any = false;
+        for (int t = s0; t < nt; ++t) {
+            const float qo = p->h_qobs[(size_t)g * nt + t] * p->cfg.dt / ((float)flw[g] * p->cfg.dx * p->cfg.dx) * 1e3f;
+            any |= qo >= 0.f;
+            valid[t] = qo >= 0.f && po[t] >= 0.f;
+        }
+        const bool live = (wgauge[g] > 0.f || wgauge[g] < 0.f) && any;
+        auto sum_po = [&](int a, int cnt) { float s = 0.f; for (int t = a; t < a + cnt; ++t) if (valid[t]) s = s + po[t]; return s; };
+        if (crc && live && !(sum_po(s0, nt - s0) > 0.f))
+            return fail(SMASHX_E_UNSUPPORTED, "Crc at gauge " + std::to_string(g + 1) + ": no precipitation > 0 on the steps with qobs >= 0 and mean_prcp >= 0; "
+                        "the reference then reads a ratio it never assigned (mwd_cost.f90:937-964)");
+        if (!ev) continue;
+        const int* mk = &G.h_mask[(size_t)g * nt];
+        for (int t = nt - 1; t >= s0; --t) if (mk[t] > 0) { nev[g] = mk[t]; break; }      // n_event = the last positive entry (:805-814)
+        evs[g].assign((size_t)2 * nev[g], 0);
+        for (int t = nt - 1; t >= s0; --t) if (mk[t] >= 1 && mk[t] <= nev[g]) { evs[g][2 * (mk[t] - 1)] = t; evs[g][2 * (mk[t] - 1) + 1]++; }
+        maxev = std::max(maxev, nev[g]);
+        if (erc && live) {
+            bool assigned = false;
+            for (int i = 0; i < nev[g] && !assigned; ++i) {
+                if (sum_po(evs[g][2 * i], evs[g][2 * i + 1]) > 0.f) assigned = true;
+                else return fail(SMASHX_E_UNSUPPORTED, "Erc at gauge " + std::to_string(g + 1) + ", event " + std::to_string(i + 1) + ": no precipitation > 0 on its valid "
+                                 "steps and no earlier event assigned the ratio; the reference then reads it unassigned (mwd_cost.f90:890-905)");
+            }
+        }
+    }
+    if (ev) {
+        if (maxev > G.maxev_cap) {
+            p->dfree(G.d_ev); p->dfree(G.a.evres); p->dfree(G.a.evcoef); p->dfree(G.a.evden); p->dfree(G.a.evflag);
+            G.d_ev = nullptr; G.a.evres = nullptr; G.a.evcoef = nullptr; G.a.evden = nullptr; G.a.evflag = nullptr; G.maxev_cap = -1;
+            int rc;
+            if ((rc = p->dmalloc(&G.d_ev, (size_t)ng * maxev * 2))) return rc;
+            if ((rc = p->dmalloc(&G.a.evres, (size_t)ng * maxev))) return rc;
+            if ((rc = p->dmalloc(&G.a.evcoef, (size_t)ng * SX_MAXJF * maxev))) return rc;
+            if ((rc = p->dmalloc(&G.a.evden, (size_t)maxev))) return rc;
+            if ((rc = p->dmalloc(&G.a.evflag, (size_t)maxev))) return rc;
+            G.maxev_cap = maxev;
+        }
+        std::vector<int> tab((size_t)std::max(1, ng * maxev * 2), 0);
+        for (int g = 0; g < ng; ++g) std::copy(evs[g].begin(), evs[g].end(), tab.begin() + (size_t)g * maxev * 2);
+        HIPCHK(hipMemcpy(G.d_ev, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(G.d_nev, nev.data(), (size_t)ng * 4, hipMemcpyHostToDevice));
+    }
+    G.a.po = G.d_po; G.a.nev = G.d_nev; G.a.ev = G.d_ev; G.a.maxev = maxev;
+    G.a.lds = 0;
+    { const char* e = getenv("SMASHX_SIG_REPLAY"); G.a.replay = (e && atoi(e) != 0) ? 1 : 0; }
+    if (pct) {
+        // the sort buffers of a gauge in LDS when the device grants them (8 B per step of the slice), else in the plan's scratch
+        const size_t need = (size_t)(nt - s0) * 8;
+        int lim = 0, dev = 0;
+        const char* force = getenv("SMASHX_SIG_LDS");          // SMASHX_SIG_LDS=0: sort in the plan's scratch whatever the length (tests)
+        if (force && atoi(force) == 0) { /* scratch */ }
+        else if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && need <= (size_t)lim) {
+            G.a.lds = 1;
+            if (need > 48 * 1024)
+                for (const void* k : {(const void*)sx_k_sig_pct, (const void*)sx_k_sig_obs})
+                    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need) != hipSuccess) { (void)hipGetLastError(); G.a.lds = 0; }
+        } else (void)hipGetLastError();
+        if (!G.a.lds && !G.a.skey) {
+            int rc;
+            if ((rc = p->dmalloc(&G.a.skey, (size_t)ng * nt))) return rc;
+            if ((rc = p->dmalloc(&G.a.sidx, (size_t)ng * nt))) return rc;
+        }
+        if (G.obs_s0 != s0 || G.obs_lds != G.a.lds) {
+            // the quantiles of the observed series: they depend on qobs and the start step alone, so a calibration loop that sets the
+            // same options before every sweep forms them once
+            SxCostArgs C = cost_args(p, 0.f);
+            C.s0 = s0; C.sig = G.a;
+            hipLaunchKernelGGL(sx_k_sig_obs, dim3(ng), dim3(64), G.a.lds ? need : 0, p->stream_r, C);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(p->stream_r));
+            G.obs_s0 = s0; G.obs_lds = G.a.lds;
+        }
+    }
+    G.a.want = (crc ? SX_SIG_WANT_CRC : 0u) | (ev ? SX_SIG_WANT_EVENTS : 0u) | (pct ? SX_SIG_WANT_PCT : 0u);
+    G.ready = true;
+    return 0;
+}
+}  // namespace
+
+int smashx_jobs_of_qsim(smashx_plan* p, const float* qsim, float jobs_b, float* jobs, float* qsim_b, const float* qsim_d, float* jobs_d) {
+    if (!p || !qsim || !jobs || (qsim_d && !jobs_d)) return fail(SMASHX_E_ARG, "null argument");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_jobs_of_qsim: a tiled plan (tile / owner_mask) is not supported");
+    int rc = set_device(p); if (rc) return rc;
+    const int ng = p->ng, nt = p->nt;
+    *jobs = 0.f; if (jobs_d) *jobs_d = 0.f;
+    if (ng == 0) return 0;
+    if (!p->have_qobs) return fail(SMASHX_E_STATE, "smashx_jobs_of_qsim: qobs not set");
+    if ((rc = signature_state(p))) return rc;
+    std::vector<char> seen(std::max(p->ngc, 1), 0);
+    for (int g = 0; g < ng; ++g) {
+        if (seen[p->gauge_gid[g]]) return fail(SMASHX_E_ARG, "smashx_jobs_of_qsim: two gauges share a cell, whose series cannot be prescribed twice");
+        seen[p->gauge_gid[g]] = 1;
+    }
+    auto& G = p->sig;
+    const size_t nq = (size_t)std::max(p->ngc, 1) * nt;
+    if (!G.d_probe_b) {
+        if ((rc = p->dmalloc(&G.d_probe_b, (size_t)ng * nt))) return rc;
+        if ((rc = p->dmalloc(&G.d_probe_gb, nq))) return rc;
+        if ((rc = p->dmalloc(&G.d_probe_gd, nq))) return rc;
+        if ((rc = p->dmalloc(&G.d_probe_keep, nq + 4))) return rc;
+    }
+    std::vector<float> rows(nq, 0.f);
+    auto to_rows = [&](const float* a) {
+        for (int g = 0; g < ng; ++g)
+            for (int t = 0; t < nt; ++t) rows[(size_t)p->gauge_gid[g] * nt + t] = a[g + (size_t)ng * t];      // (ng,nt) column-major -> [cell][t]
+    };
+    hipStream_t sR = p->stream_r;
+    // what the last sweep left -- its gauge discharges and its cost -- is put aside and put back at the end
+    HIPCHK(hipMemcpyAsync(G.d_probe_keep, p->A.qg, nq * 4, hipMemcpyDeviceToDevice, sR));
+    HIPCHK(hipMemcpyAsync(G.d_probe_keep + nq, p->d_cost_out, 4 * 4, hipMemcpyDeviceToDevice, sR));
+    to_rows(qsim);
+    HIPCHK(hipMemcpyAsync(p->A.qg, rows.data(), nq * 4, hipMemcpyHostToDevice, sR));
+    HIPCHK(hipStreamSynchronize(sR));
+    p->launches.clear(); p->pool_used = 0;
+    if ((rc = run_cost(p, qsim_b ? 1 : 0, jobs_b, G.d_probe_b, G.d_probe_gb))) return rc;
+    if (qsim_d) {
+        to_rows(qsim_d);
+        HIPCHK(hipMemcpyAsync(G.d_probe_gd, rows.data(), nq * 4, hipMemcpyHostToDevice, sR));
+        SxCostArgs C = cost_args(p, 0.f);
+        hipLaunchKernelGGL(sx_k_cost_tangent, dim3(1), dim3(64), 0, sR, C, G.d_probe_gd, p->d_cost_out + 1);
+        HIPCHK(hipMemcpyAsync(jobs_d, p->d_cost_out + 1, sizeof(float), hipMemcpyDeviceToHost, sR));
+    }
+    HIPCHK(hipMemcpyAsync(jobs, p->d_cost_out, sizeof(float), hipMemcpyDeviceToHost, sR));
+    HIPCHK(hipMemcpyAsync(p->A.qg, G.d_probe_keep, nq * 4, hipMemcpyDeviceToDevice, sR));
+    HIPCHK(hipMemcpyAsync(p->d_cost_out, G.d_probe_keep + nq, 4 * 4, hipMemcpyDeviceToDevice, sR));
+    HIPCHK(hipStreamSynchronize(sR));
+    HIPCHK(hipGetLastError());
+    if (qsim_b) {
+        std::vector<float> qb((size_t)ng * nt);
+        HIPCHK(hipMemcpy(qb.data(), G.d_probe_b, qb.size() * 4, hipMemcpyDeviceToHost));
+        for (int g = 0; g < ng; ++g)
+            for (int t = 0; t < nt; ++t) qsim_b[g + (size_t)ng * t] = qb[(size_t)g * nt + t];
+    }
+    return 0;
+}
+
+int smashx_set_signature_inputs(smashx_plan* p, const float* mean_prcp, const int* mask_event) {
+    if (!p) return fail(SMASHX_E_ARG, "null argument");
+    if (p->ng == 0) return 0;
+    if (!mean_prcp) return fail(SMASHX_E_ARG, "smashx_set_signature_inputs: mean_prcp is NULL");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_set_signature_inputs: a tiled plan (tile / owner_mask) is not supported: the criteria are sequential sums over a gauge's whole series");
+    int rc = set_device(p); if (rc) return rc;
+    const int ng = p->ng, nt = p->nt;
+    auto& G = p->sig;
+    std::vector<float> po((size_t)ng * nt);
+    std::vector<int> mk;
+    for (int g = 0; g < ng; ++g)
+        for (int t = 0; t < nt; ++t) po[(size_t)g * nt + t] = mean_prcp[g + (size_t)ng * t];       // (ng,nt) column-major -> [g][t]
+    if (mask_event) {
+        mk.resize((size_t)ng * nt);
+        for (int g = 0; g < ng; ++g)
+            for (int t = 0; t < nt; ++t) {
+                const int m = mask_event[g + (size_t)ng * t];
+                if (m < 0 || m > nt) return fail(SMASHX_E_ARG, "smashx_set_signature_inputs: mask_event holds " + std::to_string(m) + " (0 outside events, 1..n inside, n <= ntime_step)");
+                mk[(size_t)g * nt + t] = m;
+            }
+    }
+    G.ready = false;
+    if (!G.d_po) {
+        if ((rc = p->dmalloc(&G.d_po, (size_t)ng * nt))) return rc;
+        if ((rc = p->dmalloc(&G.d_nev, (size_t)ng))) return rc;
+        if ((rc = p->dmalloc(&G.a.crc, (size_t)ng * 3))) return rc;
+        if ((rc = p->dmalloc(&G.a.pct, (size_t)ng * 4))) return rc;
+        if ((rc = p->dmalloc(&G.a.den_obs, (size_t)ng * 4))) return rc;
+        if ((rc = p->dmalloc(&G.a.n_obs, (size_t)ng))) return rc;
+    }
+    if (G.have && po == G.h_po && mk == G.h_mask && G.have_mask == (mask_event != nullptr)) return 0;     // the same inputs again: nothing changes
+    HIPCHK(hipMemcpy(G.d_po, po.data(), po.size() * 4, hipMemcpyHostToDevice));
+    G.h_po.swap(po); G.h_mask.swap(mk);
+    G.have = true; G.have_mask = mask_event != nullptr;
     return 0;
 }
 
@@ -1342,11 +1576,16 @@ int smashx_set_options(smashx_plan* p, const smashx_options* o) {
     if (o->njf < 0 || o->njf > SX_MAXJF || o->njr < 0 || o->njr > 4) return fail(SMASHX_E_ARG, "njf/njr out of range");
     if (o->optimize_start_step < 1 || o->optimize_start_step > p->nt) return fail(SMASHX_E_ARG, "optimize_start_step out of range");
     for (int j = 0; j < o->njf; ++j)
-        if (o->jobs_fun[j] < SMASHX_NSE || o->jobs_fun[j] > SMASHX_LOGARITHMIC)
-            return fail(SMASHX_E_UNSUPPORTED, "signature-based jobs_fun are outside the hot path (SURVEY.md 8a a9)");
+        if (o->jobs_fun[j] < SMASHX_NSE || o->jobs_fun[j] > SMASHX_ERC)
+            return fail(SMASHX_E_UNSUPPORTED, "unknown jobs_fun (mwd_cost.f90:98-131)");
     for (int j = 0; j < o->njr; ++j)
         if (o->jreg_fun[j] < SMASHX_PRIOR || o->jreg_fun[j] > SMASHX_HARD_SMOOTHING)
             return fail(SMASHX_E_UNSUPPORTED, "unknown jreg_fun (prior / smoothing / hard_smoothing, mwd_cost.f90:199-224)");
+    {   // the signature criteria first: a refusal leaves the plan's options as they were, without the criteria's tables (run_cost checks)
+        std::vector<float> w(std::max(p->ng, 1), 0.f);
+        for (int g = 0; g < p->ng; ++g) w[g] = o->wgauge ? o->wgauge[g] : 1.f / p->ng;
+        if ((rc = prepare_signature(p, o, w))) return rc;
+    }
     p->opt = *o;
     p->jr_ready = false;
     p->opt.wgauge = nullptr;
@@ -1586,7 +1825,8 @@ static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_o
     if (!p) return fail(SMASHX_E_ARG, "null plan");
     if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
     if (!p->uploaded) return fail(SMASHX_E_STATE, "parameters/states not uploaded");
-    int rc = set_device(p); if (rc) return rc;
+    int rc = signature_state(p); if (rc) return rc;
+    if ((rc = set_device(p))) return rc;
     if ((rc = ensure_chunk_buffers(p, adjoint != 0))) return rc;
     if ((p->n_out > 0 || p->n_in > 0) && !p->halo_fn && !p->xcomm)
         return fail(SMASHX_E_STATE, "tile has boundary series but no exchange is set (smashx_set_exchange / smashx_set_halo)");
@@ -2491,6 +2731,7 @@ int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const s
     if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: denormalize_forward is not supported (the reference's multiple_run never sets it)");
     if (p->opt.wjreg != 0.f && p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: wjreg with a regulariser (jreg_fun) is not supported");
     if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: a tiled plan (tile / owner_mask) is not supported");
+    if (wants_signature(p->opt)) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: signature-based jobs_fun are not built into the ensemble cost");
     if (p->n > 65535 * SX_ENS_CELLS) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: more than 262140 active cells");
     if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
     int rc = set_device(p); if (rc) return rc;
@@ -2937,7 +3178,8 @@ int smashx_forward_d(smashx_plan* p, smashx_parameters* params, const smashx_par
     // same phases), a message per pipeline sub-chunk; the criteria's tangent covers this part's gauges, the regulariser's the whole grid
     // (smashx_tangent_terms gives the two apart: a decomposition adds the parts' first terms and counts the second once)
     if (p->tiled && p->med_nslots > 0) return fail(SMASHX_E_UNSUPPORTED, "tangent model on a tiled plan with the median over gauges of several parts");
-    int rc = smashx_upload(p, params, params_bgd, states, states_bgd); if (rc) return rc;
+    int rc = signature_state(p); if (rc) return rc;
+    if ((rc = smashx_upload(p, params, params_bgd, states, states_bgd))) return rc;
     if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
     if ((rc = set_device(p))) return rc;
     if ((rc = ensure_chunk_buffers(p, true))) return rc;

@@ -24,6 +24,26 @@ struct SxGaugeSums {   // per gauge, reference order sums
 struct SxCostCoef {    // per (gauge, cost function): what the per-element adjoint needs
     int kind;          // 0 none, 1 nse "x*c_xy + 2*y*c_yy", 4 kge "... + c_y", 2 se-like "-2*(x-y)*c", 3 logarithmic
     float c_xy, c_yy, c_y, c;
+    int i0, i1;        // signature criteria (sx_signature.h): 5 Crc "c on the masked steps", 6 Erc / 7 Epf per event, 8 Cfp* "steps i0, i1"
+};
+
+// signature criteria (sx_signature.h): inputs, tables built by smashx_set_options, and what their kernels leave for sx_k_cost_final
+struct SxSigFold; struct SxSigPct;
+struct SxSigArgs {
+    unsigned want;                  // SX_SIG_WANT_*; 0: no signature criterion is asked for
+    const float* po;                // [ng][nt] mean_prcp
+    int maxev;                      // events of the gauge that has most
+    const int* nev;                 // [ng] n_event of the slice from optimize_start_step on
+    const int* ev;                  // [ng][maxev][2] first step (0-based) and number of steps of every event
+    float* crc;                     // [ng][3] sum_qo, sum_qs, sum_po over the period
+    SxSigFold* evres;               // [ng][maxev]
+    float* evcoef;                  // [ng][SX_MAXJF][maxev] adjoint coefficient of every event
+    float* evden; int* evflag;      // [maxev] scratch of sx_k_cost_final's single thread
+    SxSigPct* pct;                  // [ng][4] Cfp2, Cfp10, Cfp50, Cfp90
+    float* den_obs; int* n_obs;     // [ng][4], [ng]: quantiles and length of the observed series (sx_k_sig_obs)
+    float* skey; int* sidx;         // [ng][nt] sort buffers of series that do not fit the LDS
+    int lds;                        // 1: sort in LDS
+    int replay;                     // 1: SMASHX_SIG_REPLAY, the percentiles' heap sort replayed even where the selection would do
 };
 
 struct SxCostArgs {
@@ -52,6 +72,7 @@ struct SxCostArgs {
     const int* slot;                // [ng] slot of a local negative-weight gauge, else -1
     float* medx;                    // [3 nslots]: gauge_jobs of every slot (summed over the ranks between the two phases), sorted copy, weights
     int* medx_idx;                  // [nslots] sort permutation
+    SxSigArgs sig;
 };
 
 __device__ __forceinline__ float sx_qs(const SxCostArgs& C, int g, int t) {
@@ -60,6 +81,8 @@ __device__ __forceinline__ float sx_qs(const SxCostArgs& C, int g, int t) {
 __device__ __forceinline__ float sx_qo(const SxCostArgs& C, int g, int t) {
     return C.qobs[(size_t)g * C.nt + t] * C.dt / ((float)C.gauge_flwacc[g] * C.dx * C.dx) * 1e3f;   // :90-92
 }
+
+#include "sx_signature.h"
 
 // one (observed, simulated) pair folded into the running sums, in the reference's order (mwd_cost.f90:350-590); shared by
 // sx_k_cost_sums (lanes = time steps) and the ensemble cost kernel (lanes = samples, sx_ensemble.h)
@@ -137,7 +160,7 @@ __device__ __forceinline__ void sx_kge_coef(const SxGaugeSums& S, const SxKge& k
 
 // gauge_jobs of one gauge from its sums: the weighted criteria of compute_jobs (mwd_cost.f90:98-137); shared by sx_k_cost_final and
 // the ensemble cost kernel (sx_ensemble.h)
-__device__ __forceinline__ float sx_gauge_jobs(const SxCostArgs& C, const SxGaugeSums& S) {
+__device__ __forceinline__ float sx_gauge_jobs(const SxCostArgs& C, const SxGaugeSums& S, int g = -1) {
     const bool any = S.n > 0;
     float gauge_jobs = 0.f, j_imd = 0.f;
     for (int j = 0; j < C.njf; ++j) {
@@ -153,7 +176,7 @@ __device__ __forceinline__ float sx_gauge_jobs(const SxCostArgs& C, const SxGaug
                 case 4: j_imd = S.se; break;
                 case 5: j_imd = sqrtf(S.se / n); break;
                 case 6: j_imd = S.lg; break;
-                default: break;
+                default: if (C.jobs_fun[j] >= SX_JF_CRC && g >= 0) j_imd = sx_sig_eval(C, g, j, 0.f, nullptr); break;
             }
         }
         gauge_jobs = gauge_jobs + C.wjobs_fun[j] * j_imd;
@@ -194,7 +217,7 @@ __device__ inline void sx_cost_gauge_coef(const SxCostArgs& C, int g, float gaug
     for (int j = C.njf - 1; j >= 0; --j) {
         j_imd_b = j_imd_b + C.wjobs_fun[j] * gauge_jobs_b;
         if (!any) continue;
-        SxCostCoef c; c.kind = 0; c.c_xy = c.c_yy = c.c_y = c.c = 0.f;
+        SxCostCoef c; c.kind = 0; c.c_xy = c.c_yy = c.c_y = c.c = 0.f; c.i0 = c.i1 = -1;
         switch (C.jobs_fun[j]) {
             case 1: { const float mean_x = S.sum_x / n;
                       const float den = S.sum_xx - n * mean_x * mean_x;
@@ -207,7 +230,7 @@ __device__ inline void sx_cost_gauge_coef(const SxCostArgs& C, int g, float gaug
             case 5: { const float result1 = S.se;
                       c.kind = 2; c.c = (result1 / n == 0.f) ? 0.f : j_imd_b / (n * 2.0f * sqrtf(result1 / n)); j_imd_b = 0.f; } break;
             case 6: c.kind = 3; c.c = j_imd_b; j_imd_b = 0.f; break;
-            default: break;
+            default: if (C.jobs_fun[j] >= SX_JF_CRC) { sx_sig_eval(C, g, j, j_imd_b, &c); j_imd_b = 0.f; } break;
         }
         C.coef[g * SX_MAXJF + j] = c;
     }
@@ -243,7 +266,7 @@ __global__ void sx_k_cost_final(SxCostArgs C, int adjoint, int phase = 0) {
         // seeds: the positive-weight gauges see jobs_b through their weight; the median's seed reaches a slot through its weight
         float j_imd_b2 = 0.f;
         for (int g = C.ng - 1; g >= 0; --g) {
-            for (int j = 0; j < SX_MAXJF; ++j) { SxCostCoef z; z.kind = 0; z.c_xy = z.c_yy = z.c_y = z.c = 0.f; C.coef[g * SX_MAXJF + j] = z; }
+            for (int j = 0; j < SX_MAXJF; ++j) { SxCostCoef z; z.kind = 0; z.c_xy = z.c_yy = z.c_y = z.c = 0.f; z.i0 = z.i1 = -1; C.coef[g * SX_MAXJF + j] = z; }
             const float w = C.wgauge[g];
             if (!(w > 0.f || w < 0.f)) continue;
             const float gauge_jobs_b = (w > 0.f) ? 0.f : wq[C.slot[g]] * C.jobs_b;
@@ -255,7 +278,7 @@ __global__ void sx_k_cost_final(SxCostArgs C, int adjoint, int phase = 0) {
         const float w = C.wgauge[g];
         if (!(w > 0.f || w < 0.f)) continue;
         const SxGaugeSums S = C.sums[g];
-        const float gauge_jobs = sx_gauge_jobs(C, S);
+        const float gauge_jobs = sx_gauge_jobs(C, S, g);
         if (w > 0.f) jobs = jobs + w * gauge_jobs;
         else if (phase == 1) C.medx[C.slot[g]] = gauge_jobs;
         else { arr[arr_size] = gauge_jobs; arr_b[arr_size] = 0.f; perm[arr_size] = arr_size; arr_gauge[arr_size] = g; ++arr_size; }
@@ -288,7 +311,7 @@ __global__ void sx_k_cost_final(SxCostArgs C, int adjoint, int phase = 0) {
     if (!adjoint) return;
     float j_imd_b = 0.f;   // carried across gauges exactly like the reference's scalar (forward_db.f90:2656-2704)
     for (int g = C.ng - 1; g >= 0; --g) {
-        for (int j = 0; j < SX_MAXJF; ++j) { SxCostCoef z; z.kind = 0; z.c_xy = z.c_yy = z.c_y = z.c = 0.f; C.coef[g * SX_MAXJF + j] = z; }
+        for (int j = 0; j < SX_MAXJF; ++j) { SxCostCoef z; z.kind = 0; z.c_xy = z.c_yy = z.c_y = z.c = 0.f; z.i0 = z.i1 = -1; C.coef[g * SX_MAXJF + j] = z; }
         const float w = C.wgauge[g];
         if (!(w > 0.f || w < 0.f)) continue;
         const SxGaugeSums S = C.sums[g];
@@ -322,6 +345,7 @@ __global__ void sx_k_cost_seeds(SxCostArgs C) {
                     y_b = y_b + arg2_b / x + arg1_b / x;
                 }
             }
+            else if (c.kind >= 5) y_b = sx_sig_seed(C, g, j, t, x, c, y_b);
         }
         out = 0.f + C.dt * 1e3f * y_b / C.area[g];
     }
@@ -430,6 +454,7 @@ __global__ void sx_k_cost_tangent(SxCostArgs C, const float* qgd, float* out) {
                     j_imd_d = (se / fn == 0.f) ? 0.f : se_d / (2.0f * tv * fn);
                     j_imd = tv;
                 } else if (fun == 6) { j_imd_d = lg_d; j_imd = lg; }
+                else if (fun >= SX_JF_CRC) j_imd = sx_sig_tangent(C, g, j, yd, j_imd_d);
             }
             gauge_jobs_d = gauge_jobs_d + C.wjobs_fun[j] * j_imd_d;
             gauge_jobs = gauge_jobs + C.wjobs_fun[j] * j_imd;

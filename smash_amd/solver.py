@@ -21,7 +21,7 @@ import zlib
 import numpy as np
 
 from . import _lib
-from ._lib import HYPER, JOBS_FUN, JREG_FUN, STRUCTURES
+from ._lib import HYPER, JOBS_FUN, JREG_FUN, SIGNATURE_FUN, STRUCTURES
 from .synth import PARAM_DEFAULTS, PARAM_NAMES, STATE_NAMES
 
 
@@ -221,6 +221,29 @@ class Solver:
     def set_qobs(self, qobs):
         q = _f32(qobs)
         _lib.check(_lib.lib().smashx_set_qobs(self._h, _ptr(q)))
+
+    # -- signature-based criteria ------------------------------------------------------------------
+    def set_signature_inputs(self, mean_prcp, mask_event=None):
+        """What the signature criteria read beside the discharges (include/smashx_signature.h): mean_prcp (ng, nt) float32 and
+        mask_event (ng, nt) int32, Fortran order; mask_event = None when no E* criterion will be asked for.  Call before set_options."""
+        mp, mk = check_signature_inputs(self.ng, self.nt, mean_prcp, mask_event)
+        _lib.check(_lib.lib().smashx_set_signature_inputs(self._h, _ptr(mp), _ptr(mk)))
+
+    def jobs_of_qsim(self, qsim, jobs_b=None, qsim_d=None):
+        """The cost kernels on a prescribed discharge (smashx_jobs_of_qsim): qsim (ng, nt) float32 Fortran order.  Returns
+        (jobs, qsim_b or None, jobs_d or None): qsim_b = output_b%qsim for the seed jobs_b, jobs_d the tangent along qsim_d."""
+        def bad(msg):
+            return _lib.SmashxError(_lib.E_ARG, "jobs_of_qsim: " + msg)
+        for name, a in (("qsim", qsim), ("qsim_d", qsim_d)):
+            if a is not None and (not isinstance(a, np.ndarray) or a.shape != (self.ng, self.nt) or a.dtype != np.float32 or not a.flags.f_contiguous):
+                raise bad(f"{name} must be a Fortran-ordered float32 array of shape ({self.ng}, {self.nt})")
+        if qsim is None:
+            raise bad("qsim is None")
+        qb = np.zeros((self.ng, self.nt), np.float32, order="F") if jobs_b is not None else None
+        jobs, jobs_d = C.c_float(0.0), C.c_float(0.0)
+        _lib.check(_lib.lib().smashx_jobs_of_qsim(self._h, _ptr(qsim), float(jobs_b or 0.0), C.byref(jobs), _ptr(qb), _ptr(qsim_d),
+                                                  C.byref(jobs_d) if qsim_d is not None else None))
+        return np.float32(jobs.value), qb, (np.float32(jobs_d.value) if qsim_d is not None else None)
 
     # -- tiles ---------------------------------------------------------------------------------
     def halo_counts(self):
@@ -635,6 +658,57 @@ def compute_mean_forcing(setup, mesh, input_data):
     return input_data.mean_prcp, input_data.mean_pet
 
 
+# ---- inputs of the signature-based criteria (mwd_cost.f90:82, 125-129) -----------------------------------------------------------------
+def wants_signature(jobs_fun):
+    return any(j in SIGNATURE_FUN for j in jobs_fun)
+
+
+def check_signature_inputs(ng, nt, mean_prcp, mask_event=None):
+    """Argument checks of set_signature_inputs, before anything reaches the C call (an array of another shape, type or order would be
+    read out of bounds or scrambled).  Returns (mean_prcp, mask_event) ready for the call; raises SmashxError(E_ARG)."""
+    def bad(msg):
+        return _lib.SmashxError(_lib.E_ARG, "signature inputs: " + msg)
+    if not isinstance(mean_prcp, np.ndarray) or mean_prcp.shape != (ng, nt) or mean_prcp.dtype != np.float32 or not mean_prcp.flags.f_contiguous:
+        raise bad(f"mean_prcp must be a Fortran-ordered float32 array of shape ({ng}, {nt})")
+    if mask_event is not None:
+        if not isinstance(mask_event, np.ndarray) or mask_event.shape != (ng, nt) or mask_event.dtype != np.int32 or not mask_event.flags.f_contiguous:
+            raise bad(f"mask_event must be a Fortran-ordered int32 array of shape ({ng}, {nt})")
+        if mask_event.size and (mask_event.min() < 0 or mask_event.max() > nt):
+            raise bad(f"mask_event holds entries outside 0..{nt} (0 outside events, 1..n inside)")
+    return mean_prcp, mask_event
+
+
+def signature_refusal(jobs_fun, wgauge, qobs, mean_prcp, mask_event, optimize_start_step):
+    """The refusal rule of smashx_set_options for the signature criteria (include/smashx_signature.h), on the host: the reason, or None.
+    The reference leaves num / den unassigned -- and then reads them -- for Crc when the rain summed over the steps with qobs >= 0 and
+    mean_prcp >= 0 is not > 0, and for an Erc event of which that holds when no earlier event assigned them; whether that happens
+    depends on qobs, mean_prcp and mask_event only.  Gauges with wgauge = 0 or without any qobs >= 0 are not evaluated."""
+    s0 = int(optimize_start_step) - 1
+    want = [j for j in jobs_fun if j in SIGNATURE_FUN]
+    if not want:
+        return None
+    if mean_prcp is None:
+        return "signature criteria read mean_prcp, which is missing"
+    if mask_event is None and any(j[0] == "E" for j in want):
+        return "Epf / Elt / Erc read mask_event, which is missing"
+    qobs, po = np.asarray(qobs, np.float32)[:, s0:], np.asarray(mean_prcp, np.float32)[:, s0:]
+    for g in range(qobs.shape[0]):
+        if not (wgauge[g] > 0 or wgauge[g] < 0) or not np.any(qobs[g] >= 0):
+            continue
+        valid = (qobs[g] >= 0) & (po[g] >= 0)        # (qo is qobs times a positive factor)
+        if "Crc" in want and not np.any(po[g][valid] > 0):
+            return f"Crc at gauge {g + 1}: no precipitation > 0 on the steps with qobs >= 0 and mean_prcp >= 0"
+        if "Erc" in want:
+            mk = np.asarray(mask_event)[g, s0:]
+            pos = np.flatnonzero(mk > 0)
+            for i in range(1, (int(mk[pos[-1]]) if pos.size else 0) + 1):
+                w = np.flatnonzero(mk == i)
+                if w.size and np.any(po[g][w[0]:w[0] + w.size][valid[w[0]:w[0] + w.size]] > 0):
+                    break
+                return f"Erc at gauge {g + 1}, event {i}: no precipitation > 0 on its valid steps and no earlier event assigned the ratio"
+    return None
+
+
 # ---- precipitation indices: mw_forcing_statistic::compute_prcp_indices (mw_forcing_statistic.f90:77-220) -----------------------------
 PRCP_INDICES = ("std", "d1", "d2", "vg")
 
@@ -726,6 +800,20 @@ def _solver_for(setup, mesh, input_data, options=True, **kw):
         return s
     if mesh.ng:
         s.set_qobs(input_data.qobs)
+    if mesh.ng and wants_signature(setup.optimize.jobs_fun):
+        # the criteria's inputs before the options, which decide the refusals on them; keyed on their contents like the forcing
+        # (mask_event and mean_prcp are written in place by their producers)
+        o = setup.optimize
+        events = any(j in ("Epf", "Elt", "Erc") for j in o.jobs_fun)
+        mp, mk = check_signature_inputs(mesh.ng, setup.ntime_step, getattr(input_data, "mean_prcp", None),
+                                        getattr(o, "mask_event", None) if events else None)
+        why = signature_refusal(o.jobs_fun, o.wgauge, input_data.qobs, mp, mk, o.optimize_start_step)
+        if why is not None:
+            raise _lib.SmashxError(_lib.E_UNSUPPORTED, why)
+        key = (zlib.crc32(mp.tobytes(order="A")), None if mk is None else zlib.crc32(mk.tobytes(order="A")))
+        if getattr(s, "_sig_key", None) != key:
+            s.set_signature_inputs(mp, mk)
+            s._sig_key = key
     s.set_options(setup.optimize)
     return s
 

@@ -25,7 +25,7 @@ GUB_STATES = np.array([0.999999] * 7 + [10000.0], dtype=np.float32)
 
 
 class Optimize_SetupDT:
-    def __init__(self, ng: int):
+    def __init__(self, ng: int, ntime_step: int = 0):
         self.jobs_fun = []            # njf = len(jobs_fun); plain Model.run() has none (mwd_setup.f90:236)
         self.wjobs_fun = []
         self.wjreg = 0.0
@@ -43,6 +43,9 @@ class Optimize_SetupDT:
         self.wgauge = np.full(max(ng, 1), 1.0 / max(ng, 1), np.float32)[:ng]
         self.mapping = "uniform"      # "hyper-linear" / "hyper-polynomial": smash_amd.hyper_forward(_b, _d)
         self.nhyper = 0               # 1 + nd (hyper-linear) or 1 + 2 nd (hyper-polynomial), mwd_setup.f90 / _optimize.py
+        # events of the E* signature criteria (mwd_setup.f90:103, 205-206): 0 outside events, 1..n inside; the caller's event
+        # segmentation fills it
+        self.mask_event = np.zeros((ng, int(ntime_step)), np.int32, order="F")
 
     @property
     def njf(self):
@@ -63,7 +66,7 @@ class SetupDT:
         self.sparse_storage = bool(sparse_storage)
         self.save_qsim_domain = bool(save_qsim_domain)          # mwd_setup.f90:144-145
         self.save_net_prcp_domain = bool(save_net_prcp_domain)
-        self.optimize = Optimize_SetupDT(ng)
+        self.optimize = Optimize_SetupDT(ng, self.ntime_step)
 
     def copy(self):
         return copy.deepcopy(self)
