@@ -20,6 +20,7 @@
 #include "sx_jreg.h"
 #include "sx_kernels.h"
 #include "sx_ensemble.h"
+#include "sx_fields.h"
 #include "sx_interception.h"
 #include "sx_meanforcing.h"
 #include "sx_prcpindices.h"
@@ -38,39 +39,6 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
         if (e_ != hipSuccess)                                                                           \
             return fail(SMASHX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" + __FILE__ + ":" + std::to_string(__LINE__) + ")"); \
     } while (0)
-
-// Which of the 16 / 8 fields each structure reads (smash/core/_constant.py:15-29; ci via gr_interception), by device
-// slot.  Parameter slots: 0 ci, 1 cp, 2 cft, 3 cst, 4 exc, 5 lr, 6..8 px[0..2]; vic-a puts b, cusl1, cusl2, clsl, ks in
-// slots 0..4 and ds, dsm, ws in 6..8.  State slots: 0 hi, 1 hp, 2 hft, 3 hst, 4 hlr; vic-a: husl1, husl2, hlsl in 0..2.
-const int NPS = 9, NSS = 5;
-int param_field(int st, int slot) {
-    if (st == 5) {
-        const int f[NPS] = {SMASHX_P_B, SMASHX_P_CUSL1, SMASHX_P_CUSL2, SMASHX_P_CLSL, SMASHX_P_KS, SMASHX_P_LR,
-                            SMASHX_P_DS, SMASHX_P_DSM, SMASHX_P_WS};
-        return f[slot];
-    }
-    switch (slot) {
-        case 0: return (st == 2 || st == 3) ? SMASHX_P_CI : -1;
-        case 1: return SMASHX_P_CP;
-        case 2: return SMASHX_P_CFT;
-        case 3: return st == 3 ? SMASHX_P_CST : -1;
-        case 4: return st != 4 ? SMASHX_P_EXC : -1;
-        case 5: return SMASHX_P_LR;
-        default: return -1;
-    }
-}
-int state_field(int st, int slot) {
-    if (st == 5) { const int f[NSS] = {SMASHX_S_HUSL1, SMASHX_S_HUSL2, SMASHX_S_HLSL, -1, SMASHX_S_HLR}; return f[slot]; }
-    switch (slot) {
-        case 0: return (st == 2 || st == 3) ? SMASHX_S_HI : -1;
-        case 1: return SMASHX_S_HP;
-        case 2: return SMASHX_S_HFT;
-        case 3: return st == 3 ? SMASHX_S_HST : -1;
-        default: return SMASHX_S_HLR;
-    }
-}
-int param_slot_of(int st, int f) { for (int i = 0; i < NPS; ++i) if (param_field(st, i) == f) return i; return -1; }
-int state_slot_of(int st, int f) { for (int i = 0; i < NSS; ++i) if (state_field(st, i) == f) return i; return -1; }
 
 // ---- small elementwise kernels on full (nrow*ncol) fields and on the cell vectors -------------------
 __global__ void k_denormalize(float* a, long n, float lb, float ub) {   // mwd_parameters_manipulation.f90:199
@@ -395,9 +363,8 @@ struct smashx_plan {
     long n_sparse = 0;               // length of a sparse vector = the WHOLE grid's active cells along path (= n on an untiled plan)
     float* d_stage = nullptr;        // staging for full planes
     long stage_planes = 0;
-    float* d_fullP[SMASHX_GNP] = {nullptr};
-    float* d_fullS[SMASHX_GNS] = {nullptr};
-    float* st0[5] = {nullptr};       // initial (denormalised) states in cell order
+    float* d_full[SX_NFIELDS] = {nullptr};   // full planes of the uploaded (denormalised) fields the structure reads, by field
+    float* st0[SX_NSSLOTS] = {nullptr};      // initial (denormalised) states in cell order
     float* ckpt = nullptr;           // [nchunks][5][npad]
     float* d_prcp = nullptr; float* d_pet = nullptr;
     // control vector (smashx_control_*): position of cell k among the active cells in column-major order, device staging
@@ -529,6 +496,32 @@ int set_device(const smashx_plan* p) {
     return 0;
 }
 
+// ---- fields (sx_fields.h) on this plan ------------------------------------------------------------------------------------------
+static_assert(SX_NPSLOTS == SX_ENS_NP && SX_NSSLOTS == SX_ENS_NS, "the ensemble kernels number the slots like sx_fields.h");
+// The cell vectors of a slot: its values, the values a sweep starts from (the uploaded states; a parameter's are its values) and its
+// gradient, which doubles as the tangent.  References, resolved at use: the gradient vectors are allocated on the first adjoint sweep.
+struct SlotVecs { float*& val; float*& start; float*& grad; };
+SlotVecs slot_vecs(smashx_plan* p, int slot) {
+    SxDeviceArrays& A = p->A;
+    float** const val[SX_NSLOTS] = {&A.ci, &A.cp, &A.cft, &A.cst, &A.exc, &A.lr, &A.px[0], &A.px[1], &A.px[2],
+                                    &A.hi, &A.hp, &A.hft, &A.hst, &A.hlr};
+    float** const grad[SX_NSLOTS] = {&A.ci_b, &A.cp_b, &A.cft_b, &A.cst_b, &A.exc_b, &A.lr_b, &A.px_b[0], &A.px_b[1], &A.px_b[2],
+                                     &A.hi_b, &A.hp_b, &A.hft_b, &A.hst_b, &A.hlr_b};
+    return {*val[slot], sx_slot_is_state(slot) ? p->st0[slot - SX_NPSLOTS] : *val[slot], *grad[slot]};
+}
+hipStream_t slot_stream(const smashx_plan* p, int slot) { return sx_slot_on_routing(slot) ? p->stream_r : p->stream; }
+// what the options and the caller's structures hold for field idx (0..23)
+int jreg_optim(const smashx_plan* p, int idx) {
+    return idx < SMASHX_GNP ? p->opt.optim_parameters[idx] : p->opt.optim_states[idx - SMASHX_GNP];
+}
+float field_lb(const smashx_plan* p, int idx) { return idx < SMASHX_GNP ? p->opt.lb_parameters[idx] : p->opt.lb_states[idx - SMASHX_GNP]; }
+float field_ub(const smashx_plan* p, int idx) { return idx < SMASHX_GNP ? p->opt.ub_parameters[idx] : p->opt.ub_states[idx - SMASHX_GNP]; }
+float jreg_span(const smashx_plan* p, int idx) { return field_ub(p, idx) - field_lb(p, idx); }
+float* host_plane(const smashx_parameters* params, const smashx_states* states, int idx) {     // null: no structure, or no plane in it
+    if (idx < SMASHX_GNP) return params ? params->f[idx] : nullptr;
+    return states ? states->f[idx - SMASHX_GNP] : nullptr;
+}
+
 // Levels of the river tree a routing wavefront resolves inside ONE super-step (sx_plan.h "components"): SMASHX_SUBLEVELS for the
 // rounds >= 1, SMASHX_SUBLEVELS_R0 for round 0.  Default 1 = one level per super-step.  Measured (profiles/r3_sublevels.json): with 4
 // levels the groups are 3.5 x shallower (335 -> 96 stages) and every result is bit-identical, but a super-step then runs its body four
@@ -632,10 +625,8 @@ int ensure_chunk_buffers(smashx_plan* p, bool adjoint) {
         if (st == 5 || ((st == 2 || st == 3) && p->hi_tape)) { if ((rc = p->dmalloc(&p->A.tape_hi, cs))) return rc; }
         else if (st == 2 || st == 3) { if ((rc = p->dmalloc(&p->A.ckpt_hi, cs / SX_HIK))) return rc; }
         if (st == 3) { if ((rc = p->dmalloc(&p->A.tape_hst, cs))) return rc; }
-        if (p->nchunks > 1) { if ((rc = p->dmalloc(&p->ckpt, (size_t)p->nchunks * 5 * p->npad))) return rc; }
-        float** g[14] = {&p->A.ci_b, &p->A.cp_b, &p->A.cft_b, &p->A.cst_b, &p->A.exc_b, &p->A.lr_b,
-                         &p->A.hi_b, &p->A.hp_b, &p->A.hft_b, &p->A.hst_b, &p->A.hlr_b, &p->A.px_b[0], &p->A.px_b[1], &p->A.px_b[2]};
-        for (auto q : g) if ((rc = p->dmalloc(q, (size_t)p->npad))) return rc;
+        if (p->nchunks > 1) { if ((rc = p->dmalloc(&p->ckpt, (size_t)p->nchunks * SX_NSSLOTS * p->npad))) return rc; }
+        for (int s = 0; s < SX_NSLOTS; ++s) if ((rc = p->dmalloc(&slot_vecs(p, s).grad, (size_t)p->npad))) return rc;
         if ((rc = p->dmalloc(&p->A.qgb, (size_t)std::max(p->ngc, 1) * p->nt))) return rc;
         if ((rc = p->dmalloc(&p->d_qsim_b, (size_t)std::max(p->ng, 1) * p->nt))) return rc;
         p->adj_ready = true;
@@ -692,62 +683,44 @@ SxDeviceArrays view_at(const smashx_plan* p, int off) {
     return B;
 }
 
-// vertical launches on the cell range [k0, k1) (cells are numbered in routing-group order: round 0 first)
-template <int ST>
-void launch_vert_fwd(smashx_plan* p, const SxDeviceArrays& B, bool tape, int t0, int T) {
-    const dim3 grid((B.k1 - B.k0 + SX_VBLOCK - 1) / SX_VBLOCK), block(SX_VBLOCK);
-    p->mark_begin(0, p->stream, (double)(B.k1 - B.k0) * T);
-    const bool cf = B.prcp16 != nullptr;
-    const size_t vl = p->vlds_fwd;       // unused dynamic LDS that caps the resident vertical workgroups per compute unit
-    if (tape) { if (cf) hipLaunchKernelGGL((sx_k_vert_fwd<ST, true, true>), grid, block, vl, p->stream, B, t0, T);
-                else    hipLaunchKernelGGL((sx_k_vert_fwd<ST, true, false>), grid, block, vl, p->stream, B, t0, T); }
-    else      { if (cf) hipLaunchKernelGGL((sx_k_vert_fwd<ST, false, true>), grid, block, vl, p->stream, B, t0, T);
-                else    hipLaunchKernelGGL((sx_k_vert_fwd<ST, false, false>), grid, block, vl, p->stream, B, t0, T); }
-    p->mark_end();
+// ---- vertical kernels: one dispatch per family (forward, reverse, tangent), one launch for all -----------------------------------
+// (structure, tape, compact forcing) -> kernel; vic-a (structure 5) is a row like the others
+typedef void (*VertKernel)(SxDeviceArrays, int, int);
+VertKernel vert_fwd_kernel(int st, bool tape, bool compact) {
+#define SX_GR(ST) {sx_k_vert_fwd<ST, false, false>, sx_k_vert_fwd<ST, false, true>, sx_k_vert_fwd<ST, true, false>, sx_k_vert_fwd<ST, true, true>}
+    static const VertKernel k[5][4] = {SX_GR(1), SX_GR(2), SX_GR(3), SX_GR(4),
+                                       {sx_k_vert_fwd_vic<false, false>, sx_k_vert_fwd_vic<false, true>, sx_k_vert_fwd_vic<true, false>, sx_k_vert_fwd_vic<true, true>}};
+#undef SX_GR
+    return k[st - 1][2 * tape + compact];
 }
-void vert_fwd(smashx_plan* p, int off, bool tape, int t0, int T, int k0 = 0, int k1 = -1) {
-    SxDeviceArrays B = view_at(p, off);
-    B.k0 = k0; B.k1 = k1 < 0 ? p->n : k1;
-    if (B.k1 <= B.k0) return;
-    switch (p->st) {
-        case 1: launch_vert_fwd<1>(p, B, tape, t0, T); break;
-        case 2: launch_vert_fwd<2>(p, B, tape, t0, T); break;
-        case 3: launch_vert_fwd<3>(p, B, tape, t0, T); break;
-        case 5: {
-            const dim3 grid((B.k1 - B.k0 + SX_VBLOCK - 1) / SX_VBLOCK), block(SX_VBLOCK);
-            p->mark_begin(0, p->stream, (double)(B.k1 - B.k0) * T);
-            const bool cf = B.prcp16 != nullptr;
-            if (tape) { if (cf) hipLaunchKernelGGL((sx_k_vert_fwd_vic<true, true>), grid, block, 0, p->stream, B, t0, T);
-                        else    hipLaunchKernelGGL((sx_k_vert_fwd_vic<true, false>), grid, block, 0, p->stream, B, t0, T); }
-            else      { if (cf) hipLaunchKernelGGL((sx_k_vert_fwd_vic<false, true>), grid, block, 0, p->stream, B, t0, T);
-                        else    hipLaunchKernelGGL((sx_k_vert_fwd_vic<false, false>), grid, block, 0, p->stream, B, t0, T); }
-            p->mark_end();
-        } break;
-        default: launch_vert_fwd<4>(p, B, tape, t0, T); break;
-    }
+VertKernel vert_adj_kernel(int st, bool compact) {
+    static const VertKernel k[5][2] = {{sx_k_vert_adj<1, false>, sx_k_vert_adj<1, true>}, {sx_k_vert_adj<2, false>, sx_k_vert_adj<2, true>},
+                                       {sx_k_vert_adj<3, false>, sx_k_vert_adj<3, true>}, {sx_k_vert_adj<4, false>, sx_k_vert_adj<4, true>},
+                                       {sx_k_vert_adj_vic<false>, sx_k_vert_adj_vic<true>}};
+    return k[st - 1][compact];
 }
-void vert_adj(smashx_plan* p, int off, int t0, int T, int k0 = 0, int k1 = -1) {
-    SxDeviceArrays B = view_at(p, off);
-    B.k0 = k0; B.k1 = k1 < 0 ? p->n : k1;
+VertKernel vert_tan_kernel(int st) {
+    static const VertKernel k[5] = {sx_k_vert_fwd_d<1>, sx_k_vert_fwd_d<2>, sx_k_vert_fwd_d<3>, sx_k_vert_fwd_d<4>, sx_k_vert_fwd_vic_d};
+    return k[st - 1];
+}
+// one vertical launch over every cell of the plan (cells are numbered in routing-group order: round 0 first) at local step `off` of the
+// storage chunk; kind: 0 forward / tangent, 3 reverse (timing)
+void launch_vert(smashx_plan* p, VertKernel k, int kind, size_t lds, int off, int t0, int T) {
+    const SxDeviceArrays B = view_at(p, off);
     if (B.k1 <= B.k0) return;
     const dim3 grid((B.k1 - B.k0 + SX_VBLOCK - 1) / SX_VBLOCK), block(SX_VBLOCK);
-    p->mark_begin(3, p->stream, (double)(B.k1 - B.k0) * T);
-    const bool cf = B.prcp16 != nullptr;
-    const size_t vl = p->vlds_adj;
-#define SX_VADJ(ST) do { if (cf) hipLaunchKernelGGL((sx_k_vert_adj<ST, true>), grid, block, vl, p->stream, B, t0, T); \
-                         else hipLaunchKernelGGL((sx_k_vert_adj<ST, false>), grid, block, vl, p->stream, B, t0, T); } while (0)
-    switch (p->st) {
-        case 1: SX_VADJ(1); break;
-        case 2: SX_VADJ(2); break;
-        case 3: SX_VADJ(3); break;
-        case 5: if (cf) hipLaunchKernelGGL(sx_k_vert_adj_vic<true>, grid, block, 0, p->stream, B, t0, T);
-                else hipLaunchKernelGGL(sx_k_vert_adj_vic<false>, grid, block, 0, p->stream, B, t0, T);
-                break;
-        default: SX_VADJ(4); break;
-    }
-#undef SX_VADJ
+    p->mark_begin(kind, p->stream, (double)(B.k1 - B.k0) * T);
+    hipLaunchKernelGGL(k, grid, block, lds, p->stream, B, t0, T);
     p->mark_end();
 }
+// lds: unused dynamic LDS that caps the resident vertical workgroups per compute unit (SMASHX_DEBUG_VLDS; the GR kernels only)
+void vert_fwd(smashx_plan* p, int off, bool tape, int t0, int T) {
+    launch_vert(p, vert_fwd_kernel(p->st, tape, p->A.prcp16 != nullptr), 0, p->st == 5 ? 0 : p->vlds_fwd, off, t0, T);
+}
+void vert_adj(smashx_plan* p, int off, int t0, int T) {
+    launch_vert(p, vert_adj_kernel(p->st, p->A.prcp16 != nullptr), 3, p->st == 5 ? 0 : p->vlds_adj, off, t0, T);
+}
+void vert_tan(smashx_plan* p, int off, int t0, int T) { launch_vert(p, vert_tan_kernel(p->st), 0, 0, off, t0, T); }
 double round_cells(const smashx_plan* p, int r0, int r1) {   // cells (inlets excluded) of the groups of rounds [r0, r1)
     double c = 0.0;
     for (int r = r0; r < r1; ++r) c += p->round_ncells[r];
@@ -762,17 +735,20 @@ void reset_chain_counters(smashx_plan* p, hipStream_t st) {
     (void)hipMemsetAsync(p->A.prog, 0, (size_t)p->sch.ngroups * sizeof(int), st);
     (void)hipMemsetAsync(p->A.prog + p->sch.ngroups + 1, 0, sizeof(int), st);
 }
-// the un-chained rounds [0, chain_first) of one forward pass over [t0, t0 + T): one launch per round on stream st
-void route_fwd_rounds(smashx_plan* p, int off, bool tape, int t0, int T, hipStream_t st) {
+// rounds [r0, r1) of one forward pass over [t0, t0 + T): one launch per round on stream st.  A sweep runs its un-chained rounds
+// [0, chain_first) like this.  tan: 0, or the pass of the tangent sweep over every round -- 1 values in forward_d's primal forms with
+// the hr_imd tape on, 2 tangents -- with every series in its plain row
+void route_fwd_rounds(smashx_plan* p, int off, bool tape, int t0, int T, hipStream_t st, int r0, int r1, int tan = 0) {
     SxDeviceArrays B = view_at(p, off);
     if (!p->dom_q_active) B.qdT = nullptr;
+    if (tan) B.qsk = nullptr;
     const size_t lds = (size_t)2 * p->M * sizeof(float4);
-    const int cf = chain_first(p);
-    for (int r = 0; r < cf; ++r) {
+    void (*const k)(SxDeviceArrays, int, int, int, int) = tan == 1 ? sx_k_route_fwd<true, false, 1> : tan == 2 ? sx_k_route_fwd<false, false, 2>
+                                                         : tape ? sx_k_route_fwd<true, false> : sx_k_route_fwd<false, false>;
+    for (int r = r0; r < r1; ++r) {
         const int g0 = p->sch.round_group_begin[r], ngr = p->sch.round_group_begin[r + 1] - g0;
         p->mark_begin(1, st, round_cells(p, r, r + 1) * T);
-        if (tape) hipLaunchKernelGGL((sx_k_route_fwd<true, false>), dim3(ngr), dim3(p->M), lds, st, B, g0, g0 + ngr, t0, T);
-        else      hipLaunchKernelGGL((sx_k_route_fwd<false, false>), dim3(ngr), dim3(p->M), lds, st, B, g0, g0 + ngr, t0, T);
+        hipLaunchKernelGGL(k, dim3(ngr), dim3(p->M), lds, st, B, g0, g0 + ngr, t0, T);
         p->mark_end();
     }
 }
@@ -904,17 +880,19 @@ int run_cost(smashx_plan* p, int adjoint, float cost_b, float* qsim_b = nullptr,
     return 0;
 }
 
-// the reservoir levels live on the V stream, the routing store hlr (index 4) on the R stream
-int copy_states(smashx_plan* p, float* const dst[5], float* const src[5]) {
-    for (int i = 0; i < 5; ++i)
-        if (state_field(p->st, i) >= 0)
-            HIPCHK(hipMemcpyAsync(dst[i], src[i], (size_t)p->npad * 4, hipMemcpyDeviceToDevice, i == 4 ? p->stream_r : p->stream));
+// The states of the structure between their cell vectors and a kept copy: the uploaded states (c < 0) or the checkpoint taken before
+// storage chunk c.  The reservoir levels move on the V stream, the routing store hlr on the R stream (sx_fields.h).
+int move_states(smashx_plan* p, int c, bool save) {
+    for (int s = SX_NPSLOTS; s < SX_NSLOTS; ++s) {
+        if (sx_slot_field(p->st, s) < 0) continue;
+        const SlotVecs V = slot_vecs(p, s);
+        float* const kept = c < 0 ? V.start : p->ckpt + ((size_t)c * SX_NSSLOTS + (s - SX_NPSLOTS)) * p->npad;
+        HIPCHK(hipMemcpyAsync(save ? kept : V.val, save ? V.val : kept, (size_t)p->npad * 4, hipMemcpyDeviceToDevice, slot_stream(p, s)));
+    }
     return 0;
 }
-int restore_states(smashx_plan* p, float* const src[5]) {
-    float* dst[5] = {p->A.hi, p->A.hp, p->A.hft, p->A.hst, p->A.hlr};
-    return copy_states(p, dst, src);
-}
+int restore_states(smashx_plan* p, int c = -1) { return move_states(p, c, false); }
+int checkpoint_states(smashx_plan* p, int c) { return move_states(p, c, true); }
 
 }  // namespace
 
@@ -1114,15 +1092,11 @@ int smashx_plan_create(const smashx_config* cfg, const smashx_mesh* mesh, smashx
         if (ok) { TRY(p->upload_vec(&p->d_sparse_idx, sp)); p->n_sparse = ind; }
     }
     // parameters, states, routing invariants
-    float** pf[NPS] = {&A.ci, &A.cp, &A.cft, &A.cst, &A.exc, &A.lr, &A.px[0], &A.px[1], &A.px[2]};
-    for (auto q : pf) TRY(p->dmalloc(q, (size_t)p->npad));
-    float** sf[5] = {&A.hi, &A.hp, &A.hft, &A.hst, &A.hlr};
-    for (auto q : sf) TRY(p->dmalloc(q, (size_t)p->npad));
-    for (int i = 0; i < 5; ++i) TRY(p->dmalloc(&p->st0[i], (size_t)p->npad));
+    for (int s = 0; s < SX_NSLOTS; ++s) TRY(p->dmalloc(&slot_vecs(p, s).val, (size_t)p->npad));
+    for (int i = 0; i < SX_NSSLOTS; ++i) TRY(p->dmalloc(&p->st0[i], (size_t)p->npad));
     float** rf[4] = {&A.rt_a, &A.rt_f, &A.rt_denf, &A.rt_denb};
     for (auto q : rf) TRY(p->dmalloc(q, (size_t)p->npad));
-    for (int i = 0; i < NPS; ++i) if (param_field(p->st, i) >= 0) TRY(p->dmalloc(&p->d_fullP[param_field(p->st, i)], (size_t)p->n2));
-    for (int i = 0; i < NSS; ++i) if (state_field(p->st, i) >= 0) TRY(p->dmalloc(&p->d_fullS[state_field(p->st, i)], (size_t)p->n2));
+    for (int s = 0; s < SX_NSLOTS; ++s) if (sx_slot_field(p->st, s) >= 0) TRY(p->dmalloc(&p->d_full[sx_slot_field(p->st, s)], (size_t)p->n2));
     p->stage_planes = std::max<long>(1, std::min<long>(64, (256L << 20) / (p->n2 * 4)));
     TRY(p->dmalloc(&p->d_stage, (size_t)p->n2 * p->stage_planes));
     // gauges / cost
@@ -1603,13 +1577,6 @@ int smashx_set_options(smashx_plan* p, const smashx_options* o) {
 }
 
 namespace {
-int jreg_optim(const smashx_plan* p, int idx) {
-    return idx < SMASHX_GNP ? p->opt.optim_parameters[idx] : p->opt.optim_states[idx - SMASHX_GNP];
-}
-float jreg_span(const smashx_plan* p, int idx) {
-    return idx < SMASHX_GNP ? p->opt.ub_parameters[idx] - p->opt.lb_parameters[idx]
-                            : p->opt.ub_states[idx - SMASHX_GNP] - p->opt.lb_states[idx - SMASHX_GNP];
-}
 // compute_jreg (and COMPUTE_JREG_B when adjoint) on the regularisation stream: independent of the simulation
 int run_jreg(smashx_plan* p, int adjoint, float cost_b) {
     if (!p->jr_ready) return fail(SMASHX_E_STATE, "jreg is on but the current upload carried no background fields");
@@ -1666,6 +1633,18 @@ int run_jreg(smashx_plan* p, int adjoint, float cost_b) {
     HIPCHK(hipEventRecord(p->ev_j, sJ));
     return 0;
 }
+// the regulariser's total from the sums of its chains (or their tangents): weighted sums of the chains, then parameters + states
+// (mwd_cost.f90:199-228; COMPUTE_JREG_D runs the same sums in the same order)
+float jreg_total(const smashx_plan* p, const float* sums) {
+    float pj = 0.f, sj = 0.f;
+    for (int i = 0; i < p->opt.njr; ++i) {
+        const float w = p->opt.wjreg_fun[i];
+        const float ww = p->opt.jreg_fun[i] == SMASHX_PRIOR ? w : w * w;
+        pj = pj + ww * sums[2 * i];
+        sj = sj + ww * sums[2 * i + 1];
+    }
+    return pj + sj;
+}
 }  // namespace
 
 int smashx_upload(smashx_plan* p, const smashx_parameters* params, const smashx_parameters* params_bgd,
@@ -1674,30 +1653,18 @@ int smashx_upload(smashx_plan* p, const smashx_parameters* params, const smashx_
     int rc = set_device(p); if (rc) return rc;
     const int st = p->st;
     const dim3 b(256), gfull((unsigned)((p->n2 + 255) / 256)), gk((p->n + 255) / 256);
-    float* pdst[NPS] = {p->A.ci, p->A.cp, p->A.cft, p->A.cst, p->A.exc, p->A.lr, p->A.px[0], p->A.px[1], p->A.px[2]};
-    for (int i = 0; i < NPS; ++i) {
-        const int f = param_field(st, i);
+    for (int s = 0; s < SX_NSLOTS; ++s) {
+        const int f = sx_slot_field(st, s);
         if (f < 0) continue;
-        if (!params->f[f]) {     // NULL = unchanged since the last upload (calibration loops move only the optimised fields)
-            if (!p->uploaded) return fail(SMASHX_E_ARG, "a parameter field the structure uses is NULL");
+        const float* h = host_plane(params, states, f);
+        if (!h) {     // NULL = unchanged since the last upload (calibration loops move only the optimised fields)
+            if (!p->uploaded) return fail(SMASHX_E_ARG, sx_field_is_state(f) ? "a state field the structure uses is NULL" : "a parameter field the structure uses is NULL");
             continue;
         }
-        HIPCHK(hipMemcpyAsync(p->d_fullP[f], params->f[f], (size_t)p->n2 * 4, hipMemcpyHostToDevice, p->stream));
+        HIPCHK(hipMemcpyAsync(p->d_full[f], h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, p->stream));
         if (p->opt.denormalize_forward)
-            hipLaunchKernelGGL(k_denormalize, gfull, b, 0, p->stream, p->d_fullP[f], p->n2, p->opt.lb_parameters[f], p->opt.ub_parameters[f]);
-        hipLaunchKernelGGL(k_gather, gk, b, 0, p->stream, pdst[i], p->d_fullP[f], p->d_cell_flat, p->n);
-    }
-    for (int i = 0; i < NSS; ++i) {
-        const int f = state_field(st, i);
-        if (f < 0) continue;
-        if (!states->f[f]) {
-            if (!p->uploaded) return fail(SMASHX_E_ARG, "a state field the structure uses is NULL");
-            continue;
-        }
-        HIPCHK(hipMemcpyAsync(p->d_fullS[f], states->f[f], (size_t)p->n2 * 4, hipMemcpyHostToDevice, p->stream));
-        if (p->opt.denormalize_forward)
-            hipLaunchKernelGGL(k_denormalize, gfull, b, 0, p->stream, p->d_fullS[f], p->n2, p->opt.lb_states[f], p->opt.ub_states[f]);
-        hipLaunchKernelGGL(k_gather, gk, b, 0, p->stream, p->st0[i], p->d_fullS[f], p->d_cell_flat, p->n);
+            hipLaunchKernelGGL(k_denormalize, gfull, b, 0, p->stream, p->d_full[f], p->n2, field_lb(p, f), field_ub(p, f));
+        hipLaunchKernelGGL(k_gather, gk, b, 0, p->stream, slot_vecs(p, s).start, p->d_full[f], p->d_cell_flat, p->n);
     }
     hipLaunchKernelGGL(sx_k_prep_routing, gk, b, 0, p->stream, p->A);
     p->jr_ready = false;
@@ -1707,17 +1674,15 @@ int smashx_upload(smashx_plan* p, const smashx_parameters* params, const smashx_
         if (!params_bgd || !states_bgd) return fail(SMASHX_E_ARG, "jreg needs parameters_bgd and states_bgd");
         for (int idx = 0; idx < SMASHX_GNP + SMASHX_GNS; ++idx) {
             if (jreg_optim(p, idx) <= 0) continue;
-            const bool isp = idx < SMASHX_GNP;
-            const float* h = isp ? params->f[idx] : states->f[idx - SMASHX_GNP];
-            const float* hb = isp ? params_bgd->f[idx] : states_bgd->f[idx - SMASHX_GNP];
+            const float* h = host_plane(params, states, idx);
+            const float* hb = host_plane(params_bgd, states_bgd, idx);
             if (!h || !hb) return fail(SMASHX_E_ARG, "an optimised field (optim_parameters / optim_states) or its background is NULL");
             if (!p->d_jx[idx]) {
                 if ((rc = p->dmalloc(&p->d_jx[idx], (size_t)p->n2))) return rc;
                 if ((rc = p->dmalloc(&p->d_jb[idx], (size_t)p->n2))) return rc;
                 if ((rc = p->dmalloc(&p->d_jg[idx], (size_t)p->n2))) return rc;
             }
-            const float lb = isp ? p->opt.lb_parameters[idx] : p->opt.lb_states[idx - SMASHX_GNP];
-            const float ub = isp ? p->opt.ub_parameters[idx] : p->opt.ub_states[idx - SMASHX_GNP];
+            const float lb = field_lb(p, idx), ub = field_ub(p, idx);
             HIPCHK(hipMemcpyAsync(p->d_jx[idx], h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, p->stream));
             if (p->opt.denormalize_forward) {
                 hipLaunchKernelGGL(k_denormalize, gfull, b, 0, p->stream, p->d_jx[idx], p->n2, lb, ub);
@@ -1820,238 +1785,230 @@ static int sx_halo_hook(smashx_plan* p, bool native, int phase, int t0, int T, h
     return rc2 ? fail(SMASHX_E_ARG, "halo callback failed") : 0;
 }
 
-static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_out) {
-    *stalled_out = false;
-    if (!p) return fail(SMASHX_E_ARG, "null plan");
-    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
-    if (!p->uploaded) return fail(SMASHX_E_STATE, "parameters/states not uploaded");
-    int rc = signature_state(p); if (rc) return rc;
-    if ((rc = set_device(p))) return rc;
-    if ((rc = ensure_chunk_buffers(p, adjoint != 0))) return rc;
-    if ((p->n_out > 0 || p->n_in > 0) && !p->halo_fn && !p->xcomm)
-        return fail(SMASHX_E_STATE, "tile has boundary series but no exchange is set (smashx_set_exchange / smashx_set_halo)");
+// ---- one sweep: its frame (sweep_begin / sweep_end), its parts on a small context, its schedule (sweep_once) --------------------
+namespace {
+// What every sweep over the period starts with (sweep_once, smashx_forward_d): no launch marked yet, the forcing closed, the R stream
+// behind the V stream, the stall flag of the chained launches clear (diagnostics: and the four ints a stalled launch leaves behind it,
+// which only sweep_once reports), the states back at the uploaded ones.
+int sweep_begin(smashx_plan* p, bool diagnostics) {
     p->launches.clear(); p->pool_used = 0;
-    p->buf_free.clear();             // (the previous sweep ended with both streams drained)
-    hipStream_t sV = p->stream, sR = p->stream_r;
-    if ((rc = close_forcing(p))) return rc;
-    HIPCHK(hipEventRecord(p->ev0, sV));
-    HIPCHK(hipStreamWaitEvent(sR, p->ev0, 0));
+    int rc = close_forcing(p); if (rc) return rc;
+    HIPCHK(hipEventRecord(p->ev0, p->stream));
+    HIPCHK(hipStreamWaitEvent(p->stream_r, p->ev0, 0));
     p->chain_used = false;
-    HIPCHK(hipMemsetAsync(p->A.prog + p->sch.ngroups, 0, sizeof(int), sR));   // stall flag of the chained launches
-    HIPCHK(hipMemsetAsync(p->A.prog + p->sch.ngroups + 3, 0, 4 * sizeof(int), sR));   // ... and its diagnostics
-    if (p->opt.njr > 0) {
-        HIPCHK(hipStreamWaitEvent(p->stream_j, p->ev0, 0));
-        if ((rc = run_jreg(p, adjoint, cost_b))) return rc;
+    HIPCHK(hipMemsetAsync(p->A.prog + p->sch.ngroups, 0, sizeof(int), p->stream_r));   // stall flag of the chained launches
+    if (diagnostics) HIPCHK(hipMemsetAsync(p->A.prog + p->sch.ngroups + 3, 0, 4 * sizeof(int), p->stream_r));   // ... and its diagnostics
+    return restore_states(p);
+}
+// ... and ends with: both streams drained, the launches' errors collected, the stall flag read if a chained launch ran
+int sweep_end(smashx_plan* p, bool* stalled) {
+    *stalled = false;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream_r));
+    HIPCHK(hipGetLastError());
+    if (p->chain_used) {
+        int flag = 0;
+        HIPCHK(hipMemcpy(&flag, p->A.prog + p->sch.ngroups, sizeof(int), hipMemcpyDeviceToHost));
+        *stalled = flag != 0;
     }
-    if ((rc = restore_states(p, p->st0))) return rc;
-    const int C = p->nchunks;
-    auto nsub_of = [&](int T) { return (T + p->Tp - 1) / p->Tp; };
-    // forward over one storage chunk: V(j) on the V stream, R(j) on the R stream as soon as V(j) is done
-    const bool native = p->xcomm != nullptr;
-    const bool halo = (p->halo_fn || native) && (p->n_out > 0 || p->n_in > 0);
-    auto halo_move = [&](bool pack, bool out_edges, int off, int T, hipStream_t st) { sx_halo_move(p, native, p->A.xT, pack, out_edges, off, T, st); };
-    auto hook = [&](int phase, int t0, int T, hipStream_t st) -> int { return sx_halo_hook(p, native, phase, t0, T, st); };
+    return 0;
+}
+
+struct Sweep {
+    smashx_plan* p;
+    hipStream_t sV, sR;
+    int C;               // storage chunks
+    bool native, halo;   // the exchange runs over RCCL; boundary series are exchanged at all
+    bool keep_in;        // the inlet series of the chunks the reverse sweep recomputes are kept
+    bool keep;           // kept chain tape
+};
+Sweep sweep_context(smashx_plan* p, bool adjoint) {
+    Sweep S{p, p->stream, p->stream_r, p->nchunks, p->xcomm != nullptr, false, false, false};
+    S.halo = (p->halo_fn || S.native) && (p->n_out > 0 || p->n_in > 0);
     // Recomputation of a storage chunk (reverse sweep) needs no neighbour: the inlet series a rank received for that chunk in the first
     // pass are kept (n_in edges x Tc steps x 4 B per chunk) and unpacked again, and nothing is sent -- the ranks downstream kept theirs.
     // A sweep then changes direction twice between the ranks (forward -> reverse) instead of twice per recomputed chunk more.
-    const int ns_max = nsub_of(p->Tc);
-    const size_t keep_sub = (size_t)std::max(p->n_in, 1) * (size_t)((p->Tp + 3) / 4) * 4;      // floats of one sub-chunk's message
-    const bool keep_in = adjoint && halo && p->n_in > 0 && C > 1;
-    if (keep_in && p->x_keep_cap < keep_sub * ns_max * (size_t)(C - 1)) {
-        if (p->x_keep) p->dfree(p->x_keep);
-        p->x_keep = nullptr; p->x_keep_cap = 0;
-        if ((rc = p->dmalloc(&p->x_keep, keep_sub * ns_max * (size_t)(C - 1)))) return rc;
-        p->x_keep_cap = keep_sub * ns_max * (size_t)(C - 1);
-    }
-    // the series of the in edges for sub-chunk jb of chunk c reach the exchange rows: received (and kept), or taken from the first pass
-    auto inlet_series = [&](int c, int jb, int off, int t0, int T, bool recompute, hipStream_t st) -> int {
-        float* msg = native ? p->x_in : p->halo_in;
-        float* kept = (keep_in && c < C - 1) ? p->x_keep + ((size_t)c * ns_max + jb) * keep_sub : nullptr;
-        const size_t bytes = (size_t)p->n_in * (size_t)((T + 3) / 4) * 4 * sizeof(float);
-        if (recompute && kept) {
-            HIPCHK(hipMemcpyAsync(msg, kept, bytes, hipMemcpyDeviceToDevice, st));
-        } else {
-            if ((rc = hook(0, t0, T, st))) return rc;      // the message buffer now holds the upstream tiles' series
-            if (kept) HIPCHK(hipMemcpyAsync(kept, msg, bytes, hipMemcpyDeviceToDevice, st));
-        }
-        halo_move(false, false, off, T, st);
-        return 0;
-    };
-    static const bool early_release = []() { const char* e = getenv("SMASHX_EARLY_RELEASE"); return !(e && e[0] == '0'); }();
+    S.keep_in = adjoint && S.halo && p->n_in > 0 && S.C > 1;
     // Kept chain tape: the chained launch of the storage chunks 0 .. C - 2 tapes in the FIRST pass (where it runs under the next chunk's
     // vertical kernel) into the plan's kept rows; their recomputation then needs neither the copy into the staging rows nor the chained
     // launch -- round 0 is upstream of it, gauge discharge and cost are known, the chunk-end states come from the checkpoints -- and
     // the chained adjoint launch reads the kept rows.
-    const bool keep = adjoint && C > 1 && p->hrk && !halo && chain_first(p) < p->sch.nrounds;
-    auto kept_rows = [&](int c) -> float* { return (keep && c < C - 1) ? p->hrk + (size_t)c * (size_t)(p->Tc / 4) * (size_t)p->A.kncs * 4 : nullptr; };
-    auto forward_chunk = [&](int c, bool tape, bool recompute = false) -> int {
-        const int t0c = c * p->Tc, Tcur = chunk_len(p, c), ns = nsub_of(Tcur);
-        std::vector<hipEvent_t> ev(ns);
-        auto launch_v = [&](int jb) -> int {
-            const int off = jb * p->Tp, T = std::min(p->Tp, Tcur - off);
-            // this part of the chunk buffers was last used by the R stream in the previous pass over them (the reverse sweep ends on
-            // the V stream): wait for that sub-chunk only, so that the routing of chunk c's tail runs under chunk c + 1's first kernels
-            if (jb < (int)p->buf_free.size() && p->buf_free[jb]) { HIPCHK(hipStreamWaitEvent(sV, p->buf_free[jb], 0)); p->buf_free[jb] = nullptr; }
-            vert_fwd(p, off, tape, t0c + off, T);
-            ev[jb] = p->event(); HIPCHK(hipEventRecord(ev[jb], sV));
-            return 0;
-        };
-        // every vertical sub-chunk is queued at once: they only depend on each other (state carry, stream order) and write
-        // disjoint parts of the chunk buffers, so the V stream never waits for the host, which blocks in the halo hooks
-        // of the routing pipeline below (tiles) -- the vertical work then hides the pipeline fill across tiles
-        for (int jb = 0; jb < ns; ++jb) if ((rc = launch_v(jb))) return rc;
-        for (int jb = 0; jb < ns; ++jb) {
-            const int off = jb * p->Tp, T = std::min(p->Tp, Tcur - off);
-            if (halo && p->n_in > 0 && (rc = inlet_series(c, jb, off, t0c + off, T, recompute, sR))) return rc;
-            HIPCHK(hipStreamWaitEvent(sR, ev[jb], 0));
-            // The next pass over this part of the chunk buffers is a vertical kernel that overwrites qt (and, taped, the level tapes --
-            // which no forward routing launch reads): it may start as soon as the routing has READ qt.  With the chained launch on staging
-            // rows that is after round 0 and the copy pass -- the chained launch, a latency chain on a few CUs, then runs under the next
-            // storage chunk's vertical kernel (first pass of a checkpointed sweep: 3 x 3.6 ms at 2048^2); else after the whole pass.
-            if ((int)p->buf_free.size() <= jb) p->buf_free.resize(jb + 1, nullptr);
-            p->buf_free[jb] = p->event();
-            float* const hrk = kept_rows(c);
-            route_fwd_rounds(p, off, tape, t0c + off, T, sR);
-            const bool released = (hrk && recompute) ? false : route_fwd_chained(p, off, tape, t0c + off, T, sR, early_release ? p->buf_free[jb] : nullptr, hrk);
-            if (halo && p->n_out > 0 && !recompute) {       // (a recomputed chunk sends nothing: every rank kept what it received)
-                halo_move(true, true, off, T, sR);
-                if ((rc = hook(1, t0c + off, T, sR))) return rc;
-            }
-            if (!released) HIPCHK(hipEventRecord(p->buf_free[jb], sR));
-        }
-        return 0;
-    };
-    // (before a storage chunk's buffers are overwritten the V stream waits for the R stream sub-chunk by sub-chunk: buf_free in forward_chunk)
-    p->dom_q_active = !adjoint && p->h_qsim_domain && p->A.qdT;
-    // optional whole-domain stores (md_forward_structure.f90:158-194) of one storage chunk -> the caller's arrays
-    auto export_domain = [&](int c) -> int {
-        const int t0c = c * p->Tc, Tcur = chunk_len(p, c);
-        HIPCHK(hipStreamSynchronize(sV));
-        HIPCHK(hipStreamSynchronize(sR));
-        const long plane = p->dom_sparse ? p->n_sparse : p->n2;
-        const int* idx = p->dom_sparse ? p->d_sparse_idx : p->d_cell_flat;
-        const int nbmax = (int)std::max<long>(1, std::min<long>(p->stage_planes * p->n2 / plane, 1 << 15));
-        for (int which = 0; which < 2; ++which) {
-            float* host = which ? p->h_net_prcp_domain : p->h_qsim_domain;
-            const float* src = which ? p->A.qtT : p->A.qdT;
-            if (!host || !src) continue;
-            for (int tl0 = 0; tl0 < Tcur; tl0 += nbmax) {
-                const int nb = std::min(nbmax, Tcur - tl0);
-                if (!p->dom_sparse || p->tiled)      // cells this plan does not write: inactive ones (dense form), other parts' (tiles)
-                    hipLaunchKernelGGL(k_fill, dim3((unsigned)(((size_t)nb * plane + 255) / 256)), dim3(256), 0, sV, p->d_stage, -99.f, (size_t)nb * plane);
-                hipLaunchKernelGGL(k_domain_export, dim3((p->n + 255) / 256, nb), dim3(256), 0, sV, p->d_stage, src, idx, p->n, p->npad, plane, tl0, nb);
-                HIPCHK(hipMemcpyAsync(host + (size_t)(t0c + tl0) * plane, p->d_stage, (size_t)nb * plane * 4, hipMemcpyDeviceToHost, sV));
-                HIPCHK(hipStreamSynchronize(sV));
-            }
-        }
-        return 0;
-    };
-    if (!adjoint) {
-        const bool dom = p->h_qsim_domain || p->h_net_prcp_domain;
-        for (int c = 0; c < C; ++c) {
-            if ((rc = forward_chunk(c, false))) return rc;
-            if (dom && (rc = export_domain(c))) return rc;
-        }
-        if ((rc = run_cost(p, 0, 0.f))) return rc;
+    S.keep = adjoint && S.C > 1 && p->hrk && !S.halo && chain_first(p) < p->sch.nrounds;
+    return S;
+}
+int nsub_of(const smashx_plan* p, int T) { return (T + p->Tp - 1) / p->Tp; }
+size_t keep_sub(const smashx_plan* p) { return (size_t)std::max(p->n_in, 1) * (size_t)((p->Tp + 3) / 4) * 4; }      // floats of one sub-chunk's message
+float* kept_rows(const Sweep& S, int c) {
+    smashx_plan* p = S.p;
+    return (S.keep && c < S.C - 1) ? p->hrk + (size_t)c * (size_t)(p->Tc / 4) * (size_t)p->A.kncs * 4 : nullptr;
+}
+int ensure_inlet_keep(const Sweep& S) {
+    smashx_plan* p = S.p;
+    const size_t need = keep_sub(p) * nsub_of(p, p->Tc) * (size_t)(S.C - 1);
+    if (!S.keep_in || p->x_keep_cap >= need) return 0;
+    if (p->x_keep) p->dfree(p->x_keep);
+    p->x_keep = nullptr; p->x_keep_cap = 0;
+    int rc = p->dmalloc(&p->x_keep, need); if (rc) return rc;
+    p->x_keep_cap = need;
+    return 0;
+}
+
+// The exchange around the routing pass of sub-chunk jb of chunk c (exchange rows xarr: xT, or xdT for the tangents).  Inlet: the series
+// of the in edges reach the exchange rows -- received (and kept), or taken from the first pass.  Outlet: the series of the out edges leave.
+int inlet_series(const Sweep& S, float* xarr, int c, int jb, int off, int t0, int T, bool recompute) {
+    smashx_plan* p = S.p;
+    if (!S.halo || p->n_in == 0) return 0;
+    float* msg = S.native ? p->x_in : p->halo_in;
+    float* kept = (S.keep_in && c < S.C - 1) ? p->x_keep + ((size_t)c * nsub_of(p, p->Tc) + jb) * keep_sub(p) : nullptr;
+    const size_t bytes = (size_t)p->n_in * (size_t)((T + 3) / 4) * 4 * sizeof(float);
+    if (recompute && kept) {
+        HIPCHK(hipMemcpyAsync(msg, kept, bytes, hipMemcpyDeviceToDevice, S.sR));
     } else {
-        for (int c = 0; c < C; ++c) {
-            if (C > 1) {
-                float* cur[5] = {p->A.hi, p->A.hp, p->A.hft, p->A.hst, p->A.hlr};
-                float* dst[5];
-                for (int i = 0; i < 5; ++i) dst[i] = p->ckpt + ((size_t)c * 5 + i) * p->npad;
-                if ((rc = copy_states(p, dst, cur))) return rc;
-            }
-            // the last storage chunk is the first one the reverse sweep needs: it runs with the tape on straight away and
-            // is not recomputed
-            if ((rc = forward_chunk(c, c == C - 1))) return rc;
-        }
-        if ((rc = run_cost(p, 1, cost_b))) return rc;
-        {   // gradient accumulators start from what COMPUTE_COST_B left in parameters_b / states_b: zero, or the
-            // regulariser's gradient for the optimised fields (forward_db.f90:10869-10874)
-            float* gv[14] = {p->A.ci_b, p->A.cp_b, p->A.cft_b, p->A.cst_b, p->A.exc_b, p->A.hi_b, p->A.hp_b, p->A.hft_b, p->A.hst_b,
-                             p->A.lr_b, p->A.hlr_b, p->A.px_b[0], p->A.px_b[1], p->A.px_b[2]};
-            const int ps = p->st;
-            auto pfi = [&](int slot) { const int f = param_field(ps, slot); return f; };
-            auto sfi = [&](int slot) { const int f = state_field(ps, slot); return f < 0 ? -1 : SMASHX_GNP + f; };
-            const int gi[14] = {pfi(0), pfi(1), pfi(2), pfi(3), pfi(4), sfi(0), sfi(1), sfi(2), sfi(3), pfi(5), sfi(4), pfi(6), pfi(7), pfi(8)};
-            bool waited[2] = {false, false};
-            for (int q = 0; q < 14; ++q) {
-                const bool on_r = (q == 9 || q == 10);
-                hipStream_t sq = on_r ? sR : sV;
-                HIPCHK(hipMemsetAsync(gv[q], 0, (size_t)p->npad * 4, sq));
-                if (p->opt.njr > 0 && gi[q] >= 0 && jreg_optim(p, gi[q]) > 0) {
-                    if (!waited[on_r ? 1 : 0]) { HIPCHK(hipStreamWaitEvent(sq, p->ev_j, 0)); waited[on_r ? 1 : 0] = true; }
-                    hipLaunchKernelGGL(k_gather, dim3((p->n + 255) / 256), dim3(256), 0, sq, gv[q], p->d_jg[gi[q]], p->d_cell_flat, p->n);
-                }
-            }
-        }
-        if (p->ng == 0) HIPCHK(hipMemsetAsync(p->A.qgb, 0, (size_t)std::max(p->ngc, 1) * p->nt * 4, sR));
-        bool adj_queued = false;      // the chained adjoint launch of the chunk at hand is already on the R stream
-        for (int c = C - 1; c >= 0; --c) {
-            const int t0c = c * p->Tc, Tcur = chunk_len(p, c);
-            if (C > 1 && c < C - 1) {   // recompute this storage chunk with the tape on
-                float* src[5];
-                for (int i = 0; i < 5; ++i) src[i] = p->ckpt + ((size_t)c * 5 + i) * p->npad;
-                if ((rc = restore_states(p, src))) return rc;
-                if ((rc = forward_chunk(c, true, true))) return rc;
-            }
-            const int nsa = (Tcur + p->Tp - 1) / p->Tp;
-            for (int jb = nsa - 1; jb >= 0; --jb) {
-                const int off = jb * p->Tp, T = std::min(p->Tp, Tcur - off);
-                if (halo && p->n_out > 0) {
-                    if ((rc = hook(2, t0c + off, T, sR))) return rc;  // out_buf now holds the downstream tiles' adjoint contributions
-                    halo_move(false, true, off, T, sR);
-                }
-                route_adj_chained(p, off, t0c + off, T, sR, kept_rows(c), !adj_queued, true);
-                adj_queued = false;
-                route_adj_rounds(p, off, t0c + off, T, sR);
-                hipEvent_t e = p->event();
-                HIPCHK(hipEventRecord(e, sR));
-                HIPCHK(hipStreamWaitEvent(sV, e, 0));
-                // Early adjoint chain: the chained adjoint launch of the chunk below needs the kept tape, the cost seeds and the routing
-                // carry this pass has just left -- nothing its recomputation produces -- and on staging rows it writes nothing the
-                // vertical kernels or round 0 touch: queued here, it runs under this chunk's vertical adjoint and the recomputation's
-                // vertical kernel.  Its copy out of the staging rows follows round 0 of the recomputation (stream order).
-                if (jb == 0 && c > 0 && kept_rows(c - 1) && p->early_adj && p->chain && p->A.qsk) {
-                    route_adj_chained(p, 0, (c - 1) * p->Tc, chunk_len(p, c - 1), sR, kept_rows(c - 1), true, false);
-                    adj_queued = true;
-                }
-                vert_adj(p, off, t0c + off, T);
-                if (halo && p->n_in > 0) {
-                    halo_move(true, false, off, T, sR);
-                    if ((rc = hook(3, t0c + off, T, sR))) return rc;
-                }
-            }
+        int rc = sx_halo_hook(p, S.native, 0, t0, T, S.sR); if (rc) return rc;      // the message buffer now holds the upstream tiles' series
+        if (kept) HIPCHK(hipMemcpyAsync(kept, msg, bytes, hipMemcpyDeviceToDevice, S.sR));
+    }
+    sx_halo_move(p, S.native, xarr, false, false, off, T, S.sR);
+    return 0;
+}
+int outlet_series(const Sweep& S, float* xarr, int off, int t0, int T) {
+    smashx_plan* p = S.p;
+    if (!S.halo || p->n_out == 0) return 0;
+    sx_halo_move(p, S.native, xarr, true, true, off, T, S.sR);
+    return sx_halo_hook(p, S.native, 1, t0, T, S.sR);
+}
+
+// forward over one storage chunk: V(j) on the V stream, R(j) on the R stream as soon as V(j) is done
+// (before a storage chunk's buffers are overwritten the V stream waits for the R stream sub-chunk by sub-chunk: buf_free)
+int forward_chunk(const Sweep& S, int c, bool tape, bool recompute = false) {
+    smashx_plan* p = S.p;
+    static const bool early_release = []() { const char* e = getenv("SMASHX_EARLY_RELEASE"); return !(e && e[0] == '0'); }();
+    const int t0c = c * p->Tc, Tcur = chunk_len(p, c), ns = nsub_of(p, Tcur);
+    std::vector<hipEvent_t> ev(ns);
+    // every vertical sub-chunk is queued at once: they only depend on each other (state carry, stream order) and write
+    // disjoint parts of the chunk buffers, so the V stream never waits for the host, which blocks in the halo hooks
+    // of the routing pipeline below (tiles) -- the vertical work then hides the pipeline fill across tiles
+    for (int jb = 0; jb < ns; ++jb) {
+        const int off = jb * p->Tp, T = std::min(p->Tp, Tcur - off);
+        // this part of the chunk buffers was last used by the R stream in the previous pass over them (the reverse sweep ends on
+        // the V stream): wait for that sub-chunk only, so that the routing of chunk c's tail runs under chunk c + 1's first kernels
+        if (jb < (int)p->buf_free.size() && p->buf_free[jb]) { HIPCHK(hipStreamWaitEvent(S.sV, p->buf_free[jb], 0)); p->buf_free[jb] = nullptr; }
+        vert_fwd(p, off, tape, t0c + off, T);
+        ev[jb] = p->event(); HIPCHK(hipEventRecord(ev[jb], S.sV));
+    }
+    for (int jb = 0; jb < ns; ++jb) {
+        const int off = jb * p->Tp, T = std::min(p->Tp, Tcur - off);
+        int rc = inlet_series(S, p->A.xT, c, jb, off, t0c + off, T, recompute); if (rc) return rc;
+        HIPCHK(hipStreamWaitEvent(S.sR, ev[jb], 0));
+        // The next pass over this part of the chunk buffers is a vertical kernel that overwrites qt (and, taped, the level tapes --
+        // which no forward routing launch reads): it may start as soon as the routing has READ qt.  With the chained launch on staging
+        // rows that is after round 0 and the copy pass -- the chained launch, a latency chain on a few CUs, then runs under the next
+        // storage chunk's vertical kernel (first pass of a checkpointed sweep: 3 x 3.6 ms at 2048^2); else after the whole pass.
+        if ((int)p->buf_free.size() <= jb) p->buf_free.resize(jb + 1, nullptr);
+        p->buf_free[jb] = p->event();
+        float* const hrk = kept_rows(S, c);
+        route_fwd_rounds(p, off, tape, t0c + off, T, S.sR, 0, chain_first(p));
+        const bool released = (hrk && recompute) ? false : route_fwd_chained(p, off, tape, t0c + off, T, S.sR, early_release ? p->buf_free[jb] : nullptr, hrk);
+        if (!recompute && (rc = outlet_series(S, p->A.xT, off, t0c + off, T))) return rc;       // (a recomputed chunk sends nothing: every rank kept what it received)
+        if (!released) HIPCHK(hipEventRecord(p->buf_free[jb], S.sR));
+    }
+    return 0;
+}
+
+// optional whole-domain stores (md_forward_structure.f90:158-194) of one storage chunk -> the caller's arrays
+int export_domain(const Sweep& S, int c) {
+    smashx_plan* p = S.p;
+    const int t0c = c * p->Tc, Tcur = chunk_len(p, c);
+    HIPCHK(hipStreamSynchronize(S.sV));
+    HIPCHK(hipStreamSynchronize(S.sR));
+    const long plane = p->dom_sparse ? p->n_sparse : p->n2;
+    const int* idx = p->dom_sparse ? p->d_sparse_idx : p->d_cell_flat;
+    const int nbmax = (int)std::max<long>(1, std::min<long>(p->stage_planes * p->n2 / plane, 1 << 15));
+    for (int which = 0; which < 2; ++which) {
+        float* host = which ? p->h_net_prcp_domain : p->h_qsim_domain;
+        const float* src = which ? p->A.qtT : p->A.qdT;
+        if (!host || !src) continue;
+        for (int tl0 = 0; tl0 < Tcur; tl0 += nbmax) {
+            const int nb = std::min(nbmax, Tcur - tl0);
+            if (!p->dom_sparse || p->tiled)      // cells this plan does not write: inactive ones (dense form), other parts' (tiles)
+                hipLaunchKernelGGL(k_fill, dim3((unsigned)(((size_t)nb * plane + 255) / 256)), dim3(256), 0, S.sV, p->d_stage, -99.f, (size_t)nb * plane);
+            hipLaunchKernelGGL(k_domain_export, dim3((p->n + 255) / 256, nb), dim3(256), 0, S.sV, p->d_stage, src, idx, p->n, p->npad, plane, tl0, nb);
+            HIPCHK(hipMemcpyAsync(host + (size_t)(t0c + tl0) * plane, p->d_stage, (size_t)nb * plane * 4, hipMemcpyDeviceToHost, S.sV));
+            HIPCHK(hipStreamSynchronize(S.sV));
         }
     }
-    {
+    return 0;
+}
+
+// gradient accumulators start from what COMPUTE_COST_B left in parameters_b / states_b: zero, or the
+// regulariser's gradient for the optimised fields (forward_db.f90:10869-10874)
+int seed_gradients(const Sweep& S) {
+    smashx_plan* p = S.p;
+    bool waited[2] = {false, false};     // a stream waits for the regulariser once
+    for (const int s : SX_SEED_ORDER) {
+        const bool on_r = sx_slot_on_routing(s);
+        const int f = sx_slot_field(p->st, s);
+        float* const g = slot_vecs(p, s).grad;
+        HIPCHK(hipMemsetAsync(g, 0, (size_t)p->npad * 4, slot_stream(p, s)));
+        if (p->opt.njr > 0 && f >= 0 && jreg_optim(p, f) > 0) {
+            if (!waited[on_r]) { HIPCHK(hipStreamWaitEvent(slot_stream(p, s), p->ev_j, 0)); waited[on_r] = true; }
+            hipLaunchKernelGGL(k_gather, dim3((p->n + 255) / 256), dim3(256), 0, slot_stream(p, s), g, p->d_jg[f], p->d_cell_flat, p->n);
+        }
+    }
+    if (p->ng == 0) HIPCHK(hipMemsetAsync(p->A.qgb, 0, (size_t)std::max(p->ngc, 1) * p->nt * 4, S.sR));
+    return 0;
+}
+
+// reverse over one storage chunk, recomputed first with the tape on unless it is the last one.  *adj_queued: the chained adjoint launch
+// of this chunk is already on the R stream (in), that of the chunk below is (out)
+int reverse_chunk(const Sweep& S, int c, bool* adj_queued) {
+    smashx_plan* p = S.p;
+    const int t0c = c * p->Tc, Tcur = chunk_len(p, c);
+    int rc;
+    if (c < S.C - 1) {
+        if ((rc = restore_states(p, c))) return rc;
+        if ((rc = forward_chunk(S, c, true, true))) return rc;
+    }
+    for (int jb = nsub_of(p, Tcur) - 1; jb >= 0; --jb) {
+        const int off = jb * p->Tp, T = std::min(p->Tp, Tcur - off);
+        if (S.halo && p->n_out > 0) {
+            if ((rc = sx_halo_hook(p, S.native, 2, t0c + off, T, S.sR))) return rc;  // out_buf now holds the downstream tiles' adjoint contributions
+            sx_halo_move(p, S.native, p->A.xT, false, true, off, T, S.sR);
+        }
+        route_adj_chained(p, off, t0c + off, T, S.sR, kept_rows(S, c), !*adj_queued, true);
+        *adj_queued = false;
+        route_adj_rounds(p, off, t0c + off, T, S.sR);
         hipEvent_t e = p->event();
-        HIPCHK(hipEventRecord(e, sR));
-        HIPCHK(hipStreamWaitEvent(sV, e, 0));
-    }
-    HIPCHK(hipEventRecord(p->ev1, sV));
-    HIPCHK(hipStreamSynchronize(sV));
-    HIPCHK(hipStreamSynchronize(sR));
-    if (p->opt.njr > 0) HIPCHK(hipStreamSynchronize(p->stream_j));
-    HIPCHK(hipGetLastError());
-    if (p->chain_used) {
-        int stalled = 0;
-        HIPCHK(hipMemcpy(&stalled, p->A.prog + p->sch.ngroups, sizeof(int), hipMemcpyDeviceToHost));
-        if (stalled) {
-            if (getenv("SMASHX_VERBOSE")) {
-                int d[7] = {0};
-                (void)hipMemcpy(d, p->A.prog + p->sch.ngroups, sizeof(d), hipMemcpyDeviceToHost);
-                fprintf(stderr, "smashx: stall: group %d followed the progress of group %d, needed %d blocks, saw %d; tickets drawn %d, chained groups %d..%d, progress:",
-                        d[3] - 2, p->sch.ngroups + d[4], d[5], d[6], d[1], p->sch.round_group_begin[chain_first(p)], p->sch.ngroups - 1);
-                std::vector<int> pr(p->sch.ngroups);
-                (void)hipMemcpy(pr.data(), p->A.prog, pr.size() * sizeof(int), hipMemcpyDeviceToHost);
-                for (int g = p->sch.round_group_begin[chain_first(p)]; g < p->sch.ngroups; ++g) fprintf(stderr, " %d", pr[g]);
-                fprintf(stderr, " (n_in %d n_out %d)\n", p->n_in, p->n_out);
-            }
-            *stalled_out = true; return 0;
+        HIPCHK(hipEventRecord(e, S.sR));
+        HIPCHK(hipStreamWaitEvent(S.sV, e, 0));
+        // Early adjoint chain: the chained adjoint launch of the chunk below needs the kept tape, the cost seeds and the routing
+        // carry this pass has just left -- nothing its recomputation produces -- and on staging rows it writes nothing the
+        // vertical kernels or round 0 touch: queued here, it runs under this chunk's vertical adjoint and the recomputation's
+        // vertical kernel.  Its copy out of the staging rows follows round 0 of the recomputation (stream order).
+        if (jb == 0 && c > 0 && kept_rows(S, c - 1) && p->early_adj && p->chain && p->A.qsk) {
+            route_adj_chained(p, 0, (c - 1) * p->Tc, chunk_len(p, c - 1), S.sR, kept_rows(S, c - 1), true, false);
+            *adj_queued = true;
+        }
+        vert_adj(p, off, t0c + off, T);
+        if (S.halo && p->n_in > 0) {
+            sx_halo_move(p, S.native, p->A.xT, true, false, off, T, S.sR);
+            if ((rc = sx_halo_hook(p, S.native, 3, t0c + off, T, S.sR))) return rc;
         }
     }
-    // timing
+    return 0;
+}
+
+void report_stall(const smashx_plan* p) {
+    int d[7] = {0};
+    (void)hipMemcpy(d, p->A.prog + p->sch.ngroups, sizeof(d), hipMemcpyDeviceToHost);
+    fprintf(stderr, "smashx: stall: group %d followed the progress of group %d, needed %d blocks, saw %d; tickets drawn %d, chained groups %d..%d, progress:",
+            d[3] - 2, p->sch.ngroups + d[4], d[5], d[6], d[1], p->sch.round_group_begin[chain_first(p)], p->sch.ngroups - 1);
+    std::vector<int> pr(p->sch.ngroups);
+    (void)hipMemcpy(pr.data(), p->A.prog, pr.size() * sizeof(int), hipMemcpyDeviceToHost);
+    for (int g = p->sch.round_group_begin[chain_first(p)]; g < p->sch.ngroups; ++g) fprintf(stderr, " %d", pr[g]);
+    fprintf(stderr, " (n_in %d n_out %d)\n", p->n_in, p->n_out);
+}
+
+void collect_timing(smashx_plan* p) {
     smashx_timing& tm = p->timing;
     std::memset(&tm, 0, sizeof(tm));
     (void)hipEventElapsedTime(&tm.sweep_ms, p->ev0, p->ev1);
@@ -2076,6 +2033,63 @@ static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_o
     tm.max_stage = p->sch.max_stage;
     tm.chain_staged = (p->chain && p->A.qsk != nullptr) ? 1 : 0;
     tm.n_chained_groups = chain_first(p) < p->sch.nrounds ? p->sch.ngroups - p->sch.round_group_begin[chain_first(p)] : 0;
+}
+}  // namespace
+
+// The schedule of one sweep: first pass over the storage chunks (adjoint: a checkpoint before each, the tape on in the last), cost, then -- adjoint --
+// the seeds and the reverse pass, last chunk first, every other chunk recomputed from its checkpoint.
+static int sweep_once(smashx_plan* p, int adjoint, float cost_b, bool* stalled_out) {
+    *stalled_out = false;
+    if (!p) return fail(SMASHX_E_ARG, "null plan");
+    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
+    if (!p->uploaded) return fail(SMASHX_E_STATE, "parameters/states not uploaded");
+    int rc = signature_state(p); if (rc) return rc;
+    if ((rc = set_device(p))) return rc;
+    if ((rc = ensure_chunk_buffers(p, adjoint != 0))) return rc;
+    if ((p->n_out > 0 || p->n_in > 0) && !p->halo_fn && !p->xcomm)
+        return fail(SMASHX_E_STATE, "tile has boundary series but no exchange is set (smashx_set_exchange / smashx_set_halo)");
+    p->buf_free.clear();             // (the previous sweep ended with both streams drained)
+    if ((rc = sweep_begin(p, true))) return rc;
+    if (p->opt.njr > 0) {
+        HIPCHK(hipStreamWaitEvent(p->stream_j, p->ev0, 0));
+        if ((rc = run_jreg(p, adjoint, cost_b))) return rc;
+    }
+    const Sweep S = sweep_context(p, adjoint != 0);
+    if ((rc = ensure_inlet_keep(S))) return rc;
+    p->dom_q_active = !adjoint && p->h_qsim_domain && p->A.qdT;
+    if (!adjoint) {
+        const bool dom = p->h_qsim_domain || p->h_net_prcp_domain;
+        for (int c = 0; c < S.C; ++c) {
+            if ((rc = forward_chunk(S, c, false))) return rc;
+            if (dom && (rc = export_domain(S, c))) return rc;
+        }
+        if ((rc = run_cost(p, 0, 0.f))) return rc;
+    } else {
+        for (int c = 0; c < S.C; ++c) {
+            if (S.C > 1 && (rc = checkpoint_states(p, c))) return rc;
+            // the last storage chunk is the first one the reverse sweep needs: it runs with the tape on straight away and
+            // is not recomputed
+            if ((rc = forward_chunk(S, c, c == S.C - 1))) return rc;
+        }
+        if ((rc = run_cost(p, 1, cost_b))) return rc;
+        if ((rc = seed_gradients(S))) return rc;
+        bool adj_queued = false;
+        for (int c = S.C - 1; c >= 0; --c)
+            if ((rc = reverse_chunk(S, c, &adj_queued))) return rc;
+    }
+    {
+        hipEvent_t e = p->event();
+        HIPCHK(hipEventRecord(e, S.sR));
+        HIPCHK(hipStreamWaitEvent(S.sV, e, 0));
+    }
+    HIPCHK(hipEventRecord(p->ev1, S.sV));
+    if (p->opt.njr > 0) HIPCHK(hipStreamSynchronize(p->stream_j));
+    if ((rc = sweep_end(p, stalled_out))) return rc;
+    if (*stalled_out) {
+        if (getenv("SMASHX_VERBOSE")) report_stall(p);
+        return 0;
+    }
+    collect_timing(p);
     p->last_adjoint = adjoint;
     return 0;
 }
@@ -2412,8 +2426,7 @@ int smashx_set_exchange(smashx_plan* p, void* comm, const int* out_peer, const i
 namespace {
 int ctrl_fields(const smashx_plan* p, int* idx) {     // flagged fields the structure uses: parameters (0..15) then states (16..23)
     int nf = 0;
-    for (int f = 0; f < SMASHX_GNP; ++f) if (p->opt.optim_parameters[f] > 0) idx[nf++] = f;
-    for (int f = 0; f < SMASHX_GNS; ++f) if (p->opt.optim_states[f] > 0) idx[nf++] = SMASHX_GNP + f;
+    for (int f = 0; f < SX_NFIELDS; ++f) if (jreg_optim(p, f) > 0) idx[nf++] = f;
     return nf;
 }
 int ctrl_prepare(smashx_plan* p, int nf) {
@@ -2436,19 +2449,9 @@ int ctrl_prepare(smashx_plan* p, int nf) {
 }
 struct CtrlField { float* cellv; float* full; float lb, ub; bool used; };
 CtrlField ctrl_field(smashx_plan* p, int idx, bool grad) {
-    CtrlField F{nullptr, nullptr, 0.f, 1.f, false};
-    float* pv[NPS] = {p->A.ci, p->A.cp, p->A.cft, p->A.cst, p->A.exc, p->A.lr, p->A.px[0], p->A.px[1], p->A.px[2]};
-    float* pg[NPS] = {p->A.ci_b, p->A.cp_b, p->A.cft_b, p->A.cst_b, p->A.exc_b, p->A.lr_b, p->A.px_b[0], p->A.px_b[1], p->A.px_b[2]};
-    float* sg[5] = {p->A.hi_b, p->A.hp_b, p->A.hft_b, p->A.hst_b, p->A.hlr_b};
-    if (idx < SMASHX_GNP) {
-        const int i = param_slot_of(p->st, idx);
-        F.lb = p->opt.lb_parameters[idx]; F.ub = p->opt.ub_parameters[idx];
-        if (i >= 0) { F.cellv = grad ? pg[i] : pv[i]; F.full = p->d_fullP[idx]; F.used = true; }
-    } else {
-        const int f = idx - SMASHX_GNP, i = state_slot_of(p->st, f);
-        F.lb = p->opt.lb_states[f]; F.ub = p->opt.ub_states[f];
-        if (i >= 0) { F.cellv = grad ? sg[i] : p->st0[i]; F.full = p->d_fullS[f]; F.used = true; }
-    }
+    CtrlField F{nullptr, nullptr, field_lb(p, idx), field_ub(p, idx), false};
+    const int s = sx_field_slot(p->st, idx);
+    if (s >= 0) { const SlotVecs V = slot_vecs(p, s); F.cellv = grad ? V.grad : V.start; F.full = p->d_full[idx]; F.used = true; }
     return F;
 }
 }  // namespace
@@ -2539,30 +2542,23 @@ int smashx_download(smashx_plan* p, int adjoint, smashx_parameters* params, smas
         float jobs = 0.f;
         if (p->ng > 0) HIPCHK(hipMemcpy(&jobs, p->d_cost_out, 4, hipMemcpyDeviceToHost));
         float jreg = 0.f;
-        if (p->opt.njr > 0) {                        // mwd_cost.f90:199-228: weighted sums of the chains, then parameters + states
+        if (p->opt.njr > 0) {
             float sums[SX_JREG_MAXCHAIN] = {0.f};
             HIPCHK(hipMemcpy(sums, p->d_jsum, sizeof(float) * 2 * p->opt.njr, hipMemcpyDeviceToHost));
-            float pj = 0.f, sj = 0.f;
-            for (int i = 0; i < p->opt.njr; ++i) {
-                const float w = p->opt.wjreg_fun[i];
-                const float ww = p->opt.jreg_fun[i] == SMASHX_PRIOR ? w : w * w;
-                pj = pj + ww * sums[2 * i];
-                sj = sj + ww * sums[2 * i + 1];
-            }
-            jreg = pj + sj;
+            jreg = jreg_total(p, sums);
         }
         costs->cost = jobs + p->opt.wjreg * jreg;    // mwd_cost.f90:300
         costs->cost_jobs = jobs; costs->cost_jreg = jreg;
     }
     // final states: output%fstates = states (forward.f90:71); inactive cells keep their entry values
     if (fstates && !adjoint) {
-        float* cur[5] = {p->A.hi, p->A.hp, p->A.hft, p->A.hst, p->A.hlr};
-        for (int i = 0; i < NSS; ++i) {
-            const int f = state_field(st, i);
-            if (f < 0 || !fstates->f[f]) continue;
-            HIPCHK(hipMemcpyAsync(p->d_stage, p->d_fullS[f], (size_t)p->n2 * 4, hipMemcpyDeviceToDevice, p->stream));
-            hipLaunchKernelGGL(k_scatter, gk, b, 0, p->stream, p->d_stage, cur[i], p->d_cell_flat, p->n, 1.f, 0);
-            HIPCHK(hipMemcpyAsync(fstates->f[f], p->d_stage, (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
+        for (int s = SX_NPSLOTS; s < SX_NSLOTS; ++s) {
+            const int f = sx_slot_field(st, s);
+            float* const h = f < 0 ? nullptr : host_plane(nullptr, fstates, f);
+            if (!h) continue;
+            HIPCHK(hipMemcpyAsync(p->d_stage, p->d_full[f], (size_t)p->n2 * 4, hipMemcpyDeviceToDevice, p->stream));
+            hipLaunchKernelGGL(k_scatter, gk, b, 0, p->stream, p->d_stage, slot_vecs(p, s).val, p->d_cell_flat, p->n, 1.f, 0);
+            HIPCHK(hipMemcpyAsync(h, p->d_stage, (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
             HIPCHK(hipStreamSynchronize(p->stream));
         }
     }
@@ -2570,72 +2566,35 @@ int smashx_download(smashx_plan* p, int adjoint, smashx_parameters* params, smas
     // denormalised; base_forward additionally sends them through normalise -> denormalise inside compute_cost.
     if (p->opt.denormalize_forward) {
         bool touched = false;
-        for (int i = 0; i < NPS; ++i) {
-            const int f = param_field(st, i);
-            if (f < 0 || !params || !params->f[f]) continue;
+        for (int s = 0; s < SX_NSLOTS; ++s) {
+            const int f = sx_slot_field(st, s);
+            float* const h = f < 0 ? nullptr : host_plane(params, states, f);
+            if (!h) continue;
             touched = true;
             if (!adjoint) {
-                hipLaunchKernelGGL(k_normalize, gfull, b, 0, p->stream, p->d_fullP[f], p->n2, p->opt.lb_parameters[f], p->opt.ub_parameters[f]);
-                hipLaunchKernelGGL(k_denormalize, gfull, b, 0, p->stream, p->d_fullP[f], p->n2, p->opt.lb_parameters[f], p->opt.ub_parameters[f]);
+                hipLaunchKernelGGL(k_normalize, gfull, b, 0, p->stream, p->d_full[f], p->n2, field_lb(p, f), field_ub(p, f));
+                hipLaunchKernelGGL(k_denormalize, gfull, b, 0, p->stream, p->d_full[f], p->n2, field_lb(p, f), field_ub(p, f));
             }
-            HIPCHK(hipMemcpyAsync(params->f[f], p->d_fullP[f], (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
-        }
-        for (int i = 0; i < NSS; ++i) {
-            const int f = state_field(st, i);
-            if (f < 0 || !states || !states->f[f]) continue;
-            touched = true;
-            if (!adjoint) {
-                hipLaunchKernelGGL(k_normalize, gfull, b, 0, p->stream, p->d_fullS[f], p->n2, p->opt.lb_states[f], p->opt.ub_states[f]);
-                hipLaunchKernelGGL(k_denormalize, gfull, b, 0, p->stream, p->d_fullS[f], p->n2, p->opt.lb_states[f], p->opt.ub_states[f]);
-            }
-            HIPCHK(hipMemcpyAsync(states->f[f], p->d_fullS[f], (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
+            HIPCHK(hipMemcpyAsync(h, p->d_full[f], (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
         }
         HIPCHK(hipStreamSynchronize(p->stream));
         if (touched) p->uploaded = false;   // the caller now holds denormalised fields: a full upload is required before the next sweep
     }
     if (adjoint) {
         if (!p->adj_ready) return fail(SMASHX_E_STATE, "no adjoint sweep has run");
-        float* gp[NPS] = {p->A.ci_b, p->A.cp_b, p->A.cft_b, p->A.cst_b, p->A.exc_b, p->A.lr_b, p->A.px_b[0], p->A.px_b[1], p->A.px_b[2]};
-        float* gs[5] = {p->A.hi_b, p->A.hp_b, p->A.hft_b, p->A.hst_b, p->A.hlr_b};
         // parameters_b / states_b are fully overwritten (forward_db.f90:10869-10870); DENORMALIZE_*_B multiplies by (ub-lb)
-        if (params_b)
-            for (int f = 0; f < SMASHX_GNP; ++f) {
-                if (!params_b->f[f]) continue;
-                const int i = param_slot_of(st, f);
-                const bool jr = p->opt.njr > 0 && jreg_optim(p, f) > 0;      // inactive cells / unused fields: the regulariser's part
-                if (jr) hipLaunchKernelGGL(sx_k_plane_scale, gfull, b, 0, p->stream, p->d_stage, p->d_jg[f],
-                                           p->opt.ub_parameters[f] - p->opt.lb_parameters[f], p->opt.denormalize_forward, p->n2);
-                else HIPCHK(hipMemsetAsync(p->d_stage, 0, (size_t)p->n2 * 4, p->stream));
-                if (i < 0) {
-                    if (!jr) { std::memset(params_b->f[f], 0, (size_t)p->n2 * 4); continue; }
-                    HIPCHK(hipMemcpyAsync(params_b->f[f], p->d_stage, (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
-                    HIPCHK(hipStreamSynchronize(p->stream));
-                    continue;
-                }
-                hipLaunchKernelGGL(k_scatter, gk, b, 0, p->stream, p->d_stage, gp[i], p->d_cell_flat, p->n,
-                                   p->opt.ub_parameters[f] - p->opt.lb_parameters[f], p->opt.denormalize_forward);
-                HIPCHK(hipMemcpyAsync(params_b->f[f], p->d_stage, (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
-                HIPCHK(hipStreamSynchronize(p->stream));
-            }
-        if (states_b)
-            for (int f = 0; f < SMASHX_GNS; ++f) {
-                if (!states_b->f[f]) continue;
-                const int i = state_slot_of(st, f);
-                const bool jr = p->opt.njr > 0 && jreg_optim(p, SMASHX_GNP + f) > 0;
-                if (jr) hipLaunchKernelGGL(sx_k_plane_scale, gfull, b, 0, p->stream, p->d_stage, p->d_jg[SMASHX_GNP + f],
-                                           p->opt.ub_states[f] - p->opt.lb_states[f], p->opt.denormalize_forward, p->n2);
-                else HIPCHK(hipMemsetAsync(p->d_stage, 0, (size_t)p->n2 * 4, p->stream));
-                if (i < 0) {
-                    if (!jr) { std::memset(states_b->f[f], 0, (size_t)p->n2 * 4); continue; }
-                    HIPCHK(hipMemcpyAsync(states_b->f[f], p->d_stage, (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
-                    HIPCHK(hipStreamSynchronize(p->stream));
-                    continue;
-                }
-                hipLaunchKernelGGL(k_scatter, gk, b, 0, p->stream, p->d_stage, gs[i], p->d_cell_flat, p->n,
-                                   p->opt.ub_states[f] - p->opt.lb_states[f], p->opt.denormalize_forward);
-                HIPCHK(hipMemcpyAsync(states_b->f[f], p->d_stage, (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
-                HIPCHK(hipStreamSynchronize(p->stream));
-            }
+        for (int f = 0; f < SX_NFIELDS; ++f) {
+            float* const hb = host_plane(params_b, states_b, f);
+            if (!hb) continue;
+            const int s = sx_field_slot(st, f);
+            const bool jr = p->opt.njr > 0 && jreg_optim(p, f) > 0;      // inactive cells / unused fields: the regulariser's part
+            if (jr) hipLaunchKernelGGL(sx_k_plane_scale, gfull, b, 0, p->stream, p->d_stage, p->d_jg[f], jreg_span(p, f), p->opt.denormalize_forward, p->n2);
+            else HIPCHK(hipMemsetAsync(p->d_stage, 0, (size_t)p->n2 * 4, p->stream));
+            if (s < 0 && !jr) { std::memset(hb, 0, (size_t)p->n2 * 4); continue; }
+            if (s >= 0) hipLaunchKernelGGL(k_scatter, gk, b, 0, p->stream, p->d_stage, slot_vecs(p, s).grad, p->d_cell_flat, p->n, jreg_span(p, f), p->opt.denormalize_forward);
+            HIPCHK(hipMemcpyAsync(hb, p->d_stage, (size_t)p->n2 * 4, hipMemcpyDeviceToHost, p->stream));
+            HIPCHK(hipStreamSynchronize(p->stream));
+        }
     }
     HIPCHK(hipStreamSynchronize(p->stream));
     HIPCHK(hipGetLastError());
@@ -2723,7 +2682,7 @@ int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const s
     for (int j = 0; j < nfields; ++j) {
         const int f = ind[j];
         if (f < 1 || f > SMASHX_GNP + SMASHX_GNS) return fail(SMASHX_E_ARG, "smashx_multiple_run: ind_parameters_states[" + std::to_string(j) + "] = " + std::to_string(f) + " is outside 1..24");
-        const int slot = f <= SMASHX_GNP ? param_slot_of(st, f - 1) : (state_slot_of(st, f - 1 - SMASHX_GNP) < 0 ? -1 : SX_ENS_NP + state_slot_of(st, f - 1 - SMASHX_GNP));
+        const int slot = sx_field_slot(st, f - 1);
         if (slot < 0) return fail(SMASHX_E_ARG, "smashx_multiple_run: field " + std::to_string(f) + " is not used by the structure");
         if (smap[slot] >= 0) return fail(SMASHX_E_ARG, "smashx_multiple_run: field " + std::to_string(f) + " is listed twice");
         smap[slot] = j;
@@ -2745,12 +2704,12 @@ int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const s
     const dim3 b256(256), gk((n + 255) / 256);
     int used_states = 0;
     for (int slot = 0; slot < SX_ENS_NP + SX_ENS_NS; ++slot) {
-        const bool isp = slot < SX_ENS_NP;
-        const int f = isp ? param_field(st, slot) : state_field(st, slot - SX_ENS_NP);
+        const bool isp = !sx_slot_is_state(slot);
+        const int f = sx_slot_field(st, slot);
         if (f < 0) continue;
         if (!isp) used_states |= 1 << (slot - SX_ENS_NP);
         if (smap[slot] >= 0) continue;
-        const float* h = isp ? params->f[f] : states->f[f];
+        const float* h = host_plane(params, states, f);
         if (!h) return fail(SMASHX_E_ARG, std::string("smashx_multiple_run: a ") + (isp ? "parameter" : "state") + " field the structure uses is NULL and not sampled");
         HIPCHK(hipMemcpyAsync(X.plane, h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
         hipLaunchKernelGGL(k_gather, gk, b256, 0, sV, X.base + (size_t)slot * p->npad, X.plane, p->d_cell_flat, n);
@@ -3195,28 +3154,17 @@ int smashx_forward_d(smashx_plan* p, smashx_parameters* params, const smashx_par
         p->tan_ready = true;
     }
     // direction -> per-cell arrays (the gradient arrays double as tangent storage); DENORMALIZE_*_D scales by (ub - lb)
-    float* tp[NPS] = {p->A.ci_b, p->A.cp_b, p->A.cft_b, p->A.cst_b, p->A.exc_b, p->A.lr_b, p->A.px_b[0], p->A.px_b[1], p->A.px_b[2]};
-    float* ts[5] = {p->A.hi_b, p->A.hp_b, p->A.hft_b, p->A.hst_b, p->A.hlr_b};
-    for (int i = 0; i < NPS; ++i) {
-        const int f = param_field(st, i);
-        HIPCHK(hipMemsetAsync(tp[i], 0, (size_t)p->npad * 4, sV));
+    for (int s = 0; s < SX_NSLOTS; ++s) {
+        const int f = sx_slot_field(st, s);
+        float* const t = slot_vecs(p, s).grad;
+        HIPCHK(hipMemsetAsync(t, 0, (size_t)p->npad * 4, sV));
         if (f < 0) continue;
-        if (!params_d->f[f]) return fail(SMASHX_E_ARG, "a tangent field the structure uses is NULL");
-        HIPCHK(hipMemcpyAsync(p->d_stage, params_d->f[f], (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
+        const float* h = host_plane(params_d, states_d, f);
+        if (!h) return fail(SMASHX_E_ARG, "a tangent field the structure uses is NULL");
+        HIPCHK(hipMemcpyAsync(p->d_stage, h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
         if (p->opt.denormalize_forward)
-            hipLaunchKernelGGL(sx_k_plane_scale, gfull, b, 0, sV, p->d_stage, p->d_stage, p->opt.ub_parameters[f] - p->opt.lb_parameters[f], 1, p->n2);
-        hipLaunchKernelGGL(k_gather, gk, b, 0, sV, tp[i], p->d_stage, p->d_cell_flat, p->n);
-        HIPCHK(hipStreamSynchronize(sV));
-    }
-    for (int i = 0; i < 5; ++i) {
-        const int f = state_field(st, i);
-        HIPCHK(hipMemsetAsync(ts[i], 0, (size_t)p->npad * 4, sV));
-        if (f < 0) continue;
-        if (!states_d->f[f]) return fail(SMASHX_E_ARG, "a tangent field the structure uses is NULL");
-        HIPCHK(hipMemcpyAsync(p->d_stage, states_d->f[f], (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
-        if (p->opt.denormalize_forward)
-            hipLaunchKernelGGL(sx_k_plane_scale, gfull, b, 0, sV, p->d_stage, p->d_stage, p->opt.ub_states[f] - p->opt.lb_states[f], 1, p->n2);
-        hipLaunchKernelGGL(k_gather, gk, b, 0, sV, ts[i], p->d_stage, p->d_cell_flat, p->n);
+            hipLaunchKernelGGL(sx_k_plane_scale, gfull, b, 0, sV, p->d_stage, p->d_stage, jreg_span(p, f), 1, p->n2);
+        hipLaunchKernelGGL(k_gather, gk, b, 0, sV, t, p->d_stage, p->d_cell_flat, p->n);
         HIPCHK(hipStreamSynchronize(sV));
     }
     // regulariser tangent (COMPUTE_JREG_D, forward_db.f90:2810-2925): the reference's running sums in its order
@@ -3232,7 +3180,7 @@ int smashx_forward_d(smashx_plan* p, smashx_parameters* params, const smashx_par
         // tangent of the control vector as compute_cost sees it: NORMALIZE_D(DENORMALIZE_D(direction))
         for (int idx = 0; idx < SMASHX_GNP + SMASHX_GNS; ++idx) {
             if (jreg_optim(p, idx) <= 0) continue;
-            const float* h = idx < SMASHX_GNP ? params_d->f[idx] : states_d->f[idx - SMASHX_GNP];
+            const float* h = host_plane(params_d, states_d, idx);
             if (!h) return fail(SMASHX_E_ARG, "the tangent of an optimised field is NULL");
             if (!p->d_tanplane[idx]) { if ((rc = p->dmalloc(&p->d_tanplane[idx], (size_t)p->n2))) return rc; }
             HIPCHK(hipMemcpyAsync(p->d_tanplane[idx], h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
@@ -3261,66 +3209,27 @@ int smashx_forward_d(smashx_plan* p, smashx_parameters* params, const smashx_par
         HIPCHK(hipMemcpyAsync(sd, p->d_jsum, sizeof(float) * 2 * p->opt.njr, hipMemcpyDeviceToHost, sV));
         HIPCHK(hipStreamSynchronize(sV));
         HIPCHK(hipMemcpy(p->d_jsum, sums_keep, sizeof(float) * 2 * p->opt.njr, hipMemcpyHostToDevice));   // the download reads jreg from here
-        float pj = 0.f, sj = 0.f;
-        for (int i = 0; i < p->opt.njr; ++i) {
-            const float w = p->opt.wjreg_fun[i];
-            const float ww = p->opt.jreg_fun[i] == SMASHX_PRIOR ? w : w * w;
-            pj = pj + ww * sd[2 * i];
-            sj = sj + ww * sd[2 * i + 1];
-        }
-        jreg_d = pj + sj;
+        jreg_d = jreg_total(p, sd);
     }
     // sweep
-    p->launches.clear(); p->pool_used = 0;
-    if ((rc = close_forcing(p))) return rc;
-    HIPCHK(hipEventRecord(p->ev0, sV));
-    HIPCHK(hipStreamWaitEvent(sR, p->ev0, 0));
-    p->chain_used = false;
+    if ((rc = sweep_begin(p, false))) return rc;
     p->dom_q_active = false;
-    HIPCHK(hipMemsetAsync(p->A.prog + p->sch.ngroups, 0, sizeof(int), sR));
-    if ((rc = restore_states(p, p->st0))) return rc;
-    const dim3 vgrid(p->npad / SX_VBLOCK), vblock(SX_VBLOCK);
-    const size_t lds = (size_t)2 * p->M * sizeof(float4);
-    for (int c = 0; c < p->nchunks; ++c) {
+    const Sweep S = sweep_context(p, false);
+    for (int c = 0; c < S.C; ++c) {
         const int t0c = c * p->Tc, Tcur = chunk_len(p, c);
         if (c > 0) { hipEvent_t e = p->event(); HIPCHK(hipEventRecord(e, sR)); HIPCHK(hipStreamWaitEvent(sV, e, 0)); }
-        const SxDeviceArrays B = view_at(p, 0);
-        p->mark_begin(0, sV);
-        switch (st) {
-            case 1: hipLaunchKernelGGL((sx_k_vert_fwd_d<1>), vgrid, vblock, 0, sV, B, t0c, Tcur); break;
-            case 2: hipLaunchKernelGGL((sx_k_vert_fwd_d<2>), vgrid, vblock, 0, sV, B, t0c, Tcur); break;
-            case 3: hipLaunchKernelGGL((sx_k_vert_fwd_d<3>), vgrid, vblock, 0, sV, B, t0c, Tcur); break;
-            case 5: hipLaunchKernelGGL(sx_k_vert_fwd_vic_d, vgrid, vblock, 0, sV, B, t0c, Tcur); break;
-            default: hipLaunchKernelGGL((sx_k_vert_fwd_d<4>), vgrid, vblock, 0, sV, B, t0c, Tcur); break;
-        }
-        p->mark_end();
+        vert_tan(p, 0, t0c, Tcur);
         hipEvent_t e = p->event(); HIPCHK(hipEventRecord(e, sV)); HIPCHK(hipStreamWaitEvent(sR, e, 0));
         // routing: values (forward_d's primal forms, hr_imd tape on), then tangents; one launch per round.  A plan with boundary series
         // (tiles) cuts each pass into the pipeline sub-chunks its message buffers hold: receive + unpack, route, pack + send
-        const bool native = p->xcomm != nullptr;
-        const bool halo = (p->halo_fn || native) && (p->n_out > 0 || p->n_in > 0);
-        const int Tsub = halo ? p->Tp : Tcur;
+        const int Tsub = S.halo ? p->Tp : Tcur;
         for (int pass = 1; pass <= 2; ++pass)
             for (int off = 0; off < Tcur; off += Tsub) {
                 const int T = std::min(Tsub, Tcur - off);
-                SxDeviceArrays Bt = view_at(p, off); Bt.qdT = nullptr;
-                Bt.qsk = nullptr;            // one launch per round: every series in its plain row
                 float* xarr = pass == 1 ? p->A.xT : p->A.xdT;
-                if (halo && p->n_in > 0) {
-                    if ((rc = sx_halo_hook(p, native, 0, t0c + off, T, sR))) return rc;
-                    sx_halo_move(p, native, xarr, false, false, off, T, sR);
-                }
-                for (int r = 0; r < p->sch.nrounds; ++r) {
-                    const int g0 = p->sch.round_group_begin[r], ngr = p->sch.round_group_begin[r + 1] - g0;
-                    p->mark_begin(1, sR);
-                    if (pass == 1) hipLaunchKernelGGL((sx_k_route_fwd<true, false, 1>), dim3(ngr), dim3(p->M), lds, sR, Bt, g0, g0 + ngr, t0c + off, T);
-                    else           hipLaunchKernelGGL((sx_k_route_fwd<false, false, 2>), dim3(ngr), dim3(p->M), lds, sR, Bt, g0, g0 + ngr, t0c + off, T);
-                    p->mark_end();
-                }
-                if (halo && p->n_out > 0) {
-                    sx_halo_move(p, native, xarr, true, true, off, T, sR);
-                    if ((rc = sx_halo_hook(p, native, 1, t0c + off, T, sR))) return rc;
-                }
+                if ((rc = inlet_series(S, xarr, c, off / Tsub, off, t0c + off, T, false))) return rc;
+                route_fwd_rounds(p, off, pass == 1, t0c + off, T, sR, 0, p->sch.nrounds, pass);
+                if ((rc = outlet_series(S, xarr, off, t0c + off, T))) return rc;
             }
     }
     // cost (values) and its tangent in the reference's summation order
@@ -3332,14 +3241,9 @@ int smashx_forward_d(smashx_plan* p, smashx_parameters* params, const smashx_par
         hipLaunchKernelGGL(sx_k_cost_tangent, dim3(1), dim3(64), 0, sR, C, p->A.qgd, p->d_cost_out + 1);
         HIPCHK(hipMemcpyAsync(&jobs_d, p->d_cost_out + 1, sizeof(float), hipMemcpyDeviceToHost, sR));
     }
-    HIPCHK(hipStreamSynchronize(sV));
-    HIPCHK(hipStreamSynchronize(sR));
-    HIPCHK(hipGetLastError());
-    if (p->chain_used) {
-        int stalled = 0;
-        HIPCHK(hipMemcpy(&stalled, p->A.prog + p->sch.ngroups, sizeof(int), hipMemcpyDeviceToHost));
-        if (stalled) return fail(SMASHX_E_HIP, "chained routing launch stalled");
-    }
+    bool stalled = false;
+    if ((rc = sweep_end(p, &stalled))) return rc;
+    if (stalled) return fail(SMASHX_E_HIP, "chained routing launch stalled");
     *cost_d = jobs_d + p->opt.wjreg * jreg_d;                        // COMPUTE_COST_D (forward_db.f90:3248)
     p->last_jobs_d = jobs_d; p->last_jreg_d = jreg_d;
     if (qsim_d && p->ng > 0) {
