@@ -334,8 +334,9 @@ int smashx_set_exchange(smashx_plan* plan, void* comm, const int* out_peer, cons
  * BASE_HYPER_FORWARD_B / _D forward_db.f90:11231-11560, 11079-11162) are forward / forward_b / forward_d with one step in front of the
  * time loop -- every parameter (state) field is a sigmoid of a linear or polynomial form of nd catchment descriptors
  * (hyper_parameters_to_parameters mwd_parameters_manipulation.f90:304-362, hyper_states_to_states mwd_states_manipulation.f90:270-329)
- * -- and that step's tangent / adjoint (forward_db.f90:1313-1537, 2179-2369) around the sweep.  The map is host code in the reference
- * and host code here (sx_hyper.cpp: no GPU, the caller's planes, fp32 in the reference's operation order); a host composes
+ * -- and that step's tangent / adjoint (forward_db.f90:1313-1537, 2179-2369) around the sweep.  The map is host code in the reference.
+ * The functions below are its host form here (sx_hyper.cpp: no GPU, the caller's planes, fp32 in the reference's operation order);
+ * smashx_hyper.h has the map and its adjoint on the device, for calibration loops that keep the planes in HBM.  A host composes
  *     smashx_hyper_map_forward (parameters, states)  ->  smashx_forward                      (base_hyper_forward)
  *     ... -> smashx_forward_b -> smashx_hyper_map_b (parameters_b -> hyper_parameters_b, ...)  (base_hyper_forward_b)
  *     smashx_hyper_map_d -> smashx_forward_d                                                 (base_hyper_forward_d)
@@ -432,6 +433,8 @@ int smashx_lbfgsb_destroy(smashx_lbfgsb* opt);
 #include "smashx_prcp.h"
 /* ---- inputs of the signature-based criteria: declared in smashx_signature.h, likewise ---------------------------------------------------- */
 #include "smashx_signature.h"
+/* ---- hyper maps on the device (the control vector of optimize_hyper_lbfgsb): declared in smashx_hyper.h, likewise ------------------------ */
+#include "smashx_hyper.h"
 
 #ifdef __cplusplus
 }

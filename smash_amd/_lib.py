@@ -1,5 +1,5 @@
 """ctypes view of include/smashx.h, declared once: the header's constants, one class per struct (STRUCTS), one prototype per function
-(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h, PRCP_PROTOTYPES for include/smashx_prcp.h and SIGNATURE_PROTOTYPES for include/smashx_signature.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
+(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h, PRCP_PROTOTYPES for include/smashx_prcp.h, SIGNATURE_PROTOTYPES for include/smashx_signature.h and HYPER_DEVICE_PROTOTYPES for include/smashx_hyper.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
 PROTOTYPES.  Loading fails loudly when libsmashx.so is missing: there is no Python / CPU implementation of the solver behind this
 module."""
 from __future__ import annotations
@@ -181,6 +181,16 @@ SIGNATURE_PROTOTYPES = {
     "smashx_jobs_of_qsim": (_int, [ptr, ptr, _float, ptr, ptr, ptr, ptr]),
 }
 SIGNATURE_SYMBOLS = list(SIGNATURE_PROTOTYPES)
+# ---- every function of include/smashx_hyper.h (the hyper maps on the device, which smashx.h includes as well), the same way;
+# tests/test_hyper_device_cpu.py reads that header and compares
+HYPER_DEVICE_PROTOTYPES = {
+    "smashx_hyper_set_descriptors": (_int, [ptr, _int, _int, ptr]),
+    "smashx_hyper_upload": (_int, [ptr, ptr, ptr]),
+    "smashx_hyper_gradient": (_int, [ptr, ptr, ptr]),
+    "smashx_hyper_fields": (_int, [ptr, _par, _sta]),
+    "smashx_hyper_info": (_int, [ptr, ptr, ptr]),
+}
+HYPER_DEVICE_SYMBOLS = list(HYPER_DEVICE_PROTOTYPES)
 
 
 class SmashxError(RuntimeError):
@@ -201,7 +211,7 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: build the HIP library first (__graft_entry__.build()); "
                               "smash_amd has no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()) + list(SIGNATURE_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()) + list(SIGNATURE_PROTOTYPES.items()) + list(HYPER_DEVICE_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         # the structs above mirror include/smashx.h by hand: refuse a library built from another layout (a stale .so would have

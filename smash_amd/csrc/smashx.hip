@@ -24,6 +24,8 @@
 #include "sx_interception.h"
 #include "sx_meanforcing.h"
 #include "sx_prcpindices.h"
+#include "sx_hypermap.h"
+#include "sx_hyperhost.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -445,6 +447,23 @@ struct smashx_plan {
         int* d_list = nullptr; float *d_dl = nullptr, *d_d2l = nullptr; SxPiGauge* d_gauges = nullptr;
         float *d_state = nullptr, *d_out = nullptr; int* d_flag = nullptr;
     } pi;
+    // hyper maps on the device (smashx_hyper_*, sx_hypermap.h): the descriptors in plan-cell order and the host copy they are compared
+    // with, the plan cells in the order of the adjoint's sums, the hyper matrices (nh, 24), the staging rows of a span and the chains
+    struct Hyper {
+        bool have = false, mapped = false;       // descriptors set; a smashx_hyper_upload has run with them
+        bool options = false;                    // smashx_set_options has been called (the plan's default options carry no bounds)
+        int mapping = 0, nd = 0, nh = 0;
+        std::vector<float> h_desc;               // [nd][n], as gathered
+        float* d_desc = nullptr; size_t desc_cap = 0;
+        int* d_order = nullptr;
+        float* d_h = nullptr; size_t h_cap = 0;
+        float* d_terms = nullptr; size_t terms_cap = 0;
+        float* d_sums = nullptr; size_t sums_cap = 0;
+        float* d_tmp = nullptr;                  // a cell vector for the fields without a slot (smashx_hyper_fields)
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        int nchain = 0, span = 0;
+        float map_ms = 0.f, grad_ms = 0.f;
+    } hyp;
     struct Ens {
         bool tables = false;
         int nlevels = 0; std::vector<int> level_begin;
@@ -1141,6 +1160,7 @@ int smashx_plan_destroy(smashx_plan* p) {
     if (p->ev_j) (void)hipEventDestroy(p->ev_j);
     if (p->ens.ev_a) (void)hipEventDestroy(p->ens.ev_a);
     if (p->ens.ev_b) (void)hipEventDestroy(p->ens.ev_b);
+    for (hipEvent_t e : p->hyp.ev) if (e) (void)hipEventDestroy(e);
     delete p;
     return 0;
 }
@@ -1573,6 +1593,7 @@ int smashx_set_options(smashx_plan* p, const smashx_options* o) {
     }
     HIPCHK(hipMemcpy(p->d_wgauge, p->wgauge.data(), p->wgauge.size() * 4, hipMemcpyHostToDevice));
     p->have_options = true;
+    p->hyp.options = true;
     return 0;
 }
 
@@ -2805,6 +2826,165 @@ int smashx_multiple_run_info(const smashx_plan* p, int info[4], float* device_ms
     if (!p) return fail(SMASHX_E_ARG, "null plan");
     if (info) for (int i = 0; i < 4; ++i) info[i] = p->ens.info[i];
     if (device_ms) *device_ms = p->ens.device_ms;
+    return 0;
+}
+
+// ---- hyper maps on the device (include/smashx_hyper.h, sx_hypermap.h) ------------------------------------------------------------
+namespace {
+// what every smashx_hyper_* call but set_descriptors refuses, in the order of the header's table
+int hyper_refusal(const smashx_plan* p, const char* who) {
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": a tiled plan (an ordered whole-grid sum does not split across parts)");
+    if (!p->hyp.have) return fail(SMASHX_E_STATE, std::string(who) + ": no descriptors set (smashx_hyper_set_descriptors)");
+    if (!p->hyp.options) return fail(SMASHX_E_STATE, std::string(who) + ": options not set (the bounds of the maps are those of smashx_set_options)");
+    if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": denormalize_forward (base_hyper_forward does not know it)");
+    if (p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": a regulariser (hyper_compute_cost: cost = jobs)");
+    return 0;
+}
+// the fields with a slot, as one launch of the map / terms kernels
+SxHmFields hyper_slot_fields(smashx_plan* p, bool grad) {
+    SxHmFields F{};
+    for (int s = 0; s < SX_NSLOTS; ++s) {
+        const int f = sx_slot_field(p->st, s);
+        if (f < 0) continue;
+        const SlotVecs V = slot_vecs(p, s);
+        const int e = F.nf++;
+        F.field[e] = f; F.lb[e] = field_lb(p, f); F.w[e] = field_ub(p, f) - field_lb(p, f);
+        F.val[e] = V.val; F.start[e] = V.start != V.val ? V.start : nullptr; F.full[e] = p->d_full[f];
+        F.grad[e] = grad ? V.grad : nullptr;
+    }
+    return F;
+}
+int hyper_events(smashx_plan* p) {
+    for (hipEvent_t& e : p->hyp.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    return 0;
+}
+}  // namespace
+
+int smashx_hyper_set_descriptors(smashx_plan* p, int mapping, int nd, const float* descriptor) {
+    if (!p) return fail(SMASHX_E_ARG, "null plan");
+    if (const char* why = sx_hh_bad_arguments(mapping, nd)) return fail(SMASHX_E_ARG, why);
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_hyper_set_descriptors: a tiled plan (an ordered whole-grid sum does not split across parts)");
+    smashx_plan::Hyper& H = p->hyp;
+    if (nd > 0 && !descriptor) { H.have = H.mapped = false; return 0; }
+    int rc = set_device(p); if (rc) return rc;
+    std::vector<float> g;
+    sx_hh_gather(descriptor, nd, (size_t)p->n2, p->sch.cell_flat, g);
+    const int nh = sx_hh_nhyper(mapping, nd);
+    if (!H.d_order && (rc = p->upload_vec(&H.d_order, sx_hh_order(p->sch.cell_flat)))) return rc;
+    const bool same = H.have && H.nd == nd && g == H.h_desc;      // (a calibration hands the same descriptors over before every evaluation)
+    if (!same) {
+        if ((rc = ens_grow(p, &H.d_desc, &H.desc_cap, std::max<size_t>(g.size(), 1)))) return rc;
+        if (!g.empty()) HIPCHK(hipMemcpy(H.d_desc, g.data(), g.size() * 4, hipMemcpyHostToDevice));
+        H.h_desc.swap(g);
+        H.mapped = false;
+    }
+    if (H.mapping != mapping) H.mapped = false;
+    H.mapping = mapping; H.nd = nd; H.nh = nh; H.have = true;
+    return 0;
+}
+
+int smashx_hyper_upload(smashx_plan* p, const float* hyper_parameters, const float* hyper_states) {
+    if (!p || !hyper_parameters || !hyper_states) return fail(SMASHX_E_ARG, "null argument");
+    int rc = hyper_refusal(p, "smashx_hyper_upload"); if (rc) return rc;
+    if ((rc = set_device(p))) return rc;
+    smashx_plan::Hyper& H = p->hyp;
+    const int nh = H.nh;
+    if ((rc = ens_grow(p, &H.d_h, &H.h_cap, (size_t)nh * SX_NFIELDS))) return rc;
+    if ((rc = hyper_events(p))) return rc;
+    HIPCHK(hipMemcpyAsync(H.d_h, hyper_parameters, (size_t)nh * SMASHX_GNP * 4, hipMemcpyHostToDevice, p->stream));
+    HIPCHK(hipMemcpyAsync(H.d_h + (size_t)nh * SMASHX_GNP, hyper_states, (size_t)nh * SMASHX_GNS * 4, hipMemcpyHostToDevice, p->stream));
+    const SxHmFields F = hyper_slot_fields(p, false);
+    const dim3 b(256), g((p->n + 255) / 256, F.nf), gk((p->n + 255) / 256);
+    HIPCHK(hipEventRecord(H.ev[0], p->stream));
+    if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
+        hipLaunchKernelGGL(sx_k_hyper_map<true>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, nh, p->n);
+    else
+        hipLaunchKernelGGL(sx_k_hyper_map<false>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, nh, p->n);
+    HIPCHK(hipEventRecord(H.ev[1], p->stream));
+    hipLaunchKernelGGL(sx_k_prep_routing, gk, b, 0, p->stream, p->A);
+    p->jr_ready = false;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventElapsedTime(&H.map_ms, H.ev[0], H.ev[1]));
+    p->uploaded = true;
+    H.mapped = true;
+    return 0;
+}
+
+int smashx_hyper_gradient(smashx_plan* p, float* hyper_parameters_b, float* hyper_states_b) {
+    if (!p || !hyper_parameters_b || !hyper_states_b) return fail(SMASHX_E_ARG, "null argument");
+    int rc = hyper_refusal(p, "smashx_hyper_gradient"); if (rc) return rc;
+    smashx_plan::Hyper& H = p->hyp;
+    if (!H.mapped || !p->uploaded) return fail(SMASHX_E_STATE, "smashx_hyper_gradient: no smashx_hyper_upload with the descriptors the plan holds");
+    if (!(p->adj_ready && p->last_adjoint)) return fail(SMASHX_E_STATE, "smashx_hyper_gradient: the last sweep was not an adjoint sweep");
+    if ((rc = set_device(p))) return rc;
+    const int nh = H.nh;
+    const SxHmFields F = hyper_slot_fields(p, true);
+    const int nchain = F.nf * nh;
+    // cells per span: from the environment, else what keeps the staging rows at SX_HM_STAGE_BYTES
+    int span = ens_env("SMASHX_HYPER_SPAN");
+    if (span <= 0) span = (int)std::max<size_t>(1024, SX_HM_STAGE_BYTES / ((size_t)nchain * 4));
+    span = std::min(span, std::max(p->n, 1));
+    if ((rc = ens_grow(p, &H.d_terms, &H.terms_cap, (size_t)span * nchain))) return rc;
+    if ((rc = ens_grow(p, &H.d_sums, &H.sums_cap, (size_t)nchain))) return rc;
+    if ((rc = hyper_events(p))) return rc;
+    H.nchain = nchain; H.span = span;
+    HIPCHK(hipEventRecord(H.ev[2], p->stream));
+    HIPCHK(hipMemsetAsync(H.d_sums, 0, (size_t)nchain * 4, p->stream));
+    for (int c0 = 0; c0 < p->n; c0 += span) {
+        const int ns = std::min(span, p->n - c0);
+        const dim3 b(256), g((ns + 255) / 256, F.nf);
+        if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
+            hipLaunchKernelGGL(sx_k_hyper_terms<true>, g, b, 0, p->stream, F, H.d_h, H.d_desc, H.d_order, H.nd, nh, p->n, c0, ns, H.d_terms, nchain);
+        else
+            hipLaunchKernelGGL(sx_k_hyper_terms<false>, g, b, 0, p->stream, F, H.d_h, H.d_desc, H.d_order, H.nd, nh, p->n, c0, ns, H.d_terms, nchain);
+        hipLaunchKernelGGL(sx_k_hyper_walk, dim3((nchain + 63) / 64), dim3(64), 0, p->stream, H.d_terms, ns, nchain, H.d_sums, c0 > 0 ? 1 : 0);
+    }
+    HIPCHK(hipEventRecord(H.ev[3], p->stream));
+    std::vector<float> sums((size_t)nchain);
+    HIPCHK(hipMemcpyAsync(sums.data(), H.d_sums, (size_t)nchain * 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventElapsedTime(&H.grad_ms, H.ev[2], H.ev[3]));
+    sx_hh_close(sums.data(), F.field, F.nf, nh, hyper_parameters_b, hyper_states_b);
+    return 0;
+}
+
+int smashx_hyper_fields(smashx_plan* p, smashx_parameters* params, smashx_states* states) {
+    if (!p) return fail(SMASHX_E_ARG, "null plan");
+    int rc = hyper_refusal(p, "smashx_hyper_fields"); if (rc) return rc;
+    smashx_plan::Hyper& H = p->hyp;
+    if (!H.mapped) return fail(SMASHX_E_STATE, "smashx_hyper_fields: no smashx_hyper_upload with the descriptors the plan holds");
+    if ((rc = set_device(p))) return rc;
+    if (!H.d_tmp && (rc = p->dmalloc(&H.d_tmp, (size_t)std::max(p->n, 1)))) return rc;
+    std::vector<float> cellv((size_t)p->n);
+    for (int f = 0; f < SX_NFIELDS; ++f) {
+        float* const h = host_plane(params, states, f);
+        if (!h) continue;
+        const int s = sx_field_slot(p->st, f);
+        const float* src = s >= 0 ? slot_vecs(p, s).start : H.d_tmp;     // what the upload stored; mapped here for a field nothing reads
+        if (s < 0) {
+            SxHmFields F{};
+            F.nf = 1; F.field[0] = f; F.lb[0] = field_lb(p, f); F.w[0] = field_ub(p, f) - field_lb(p, f); F.val[0] = H.d_tmp;
+            const dim3 b(256), g((p->n + 255) / 256, 1);
+            if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
+                hipLaunchKernelGGL(sx_k_hyper_map<true>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, H.nh, p->n);
+            else
+                hipLaunchKernelGGL(sx_k_hyper_map<false>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, H.nh, p->n);
+        }
+        HIPCHK(hipMemcpyAsync(cellv.data(), src, (size_t)p->n * 4, hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        sx_hh_scatter(cellv.data(), p->sch.cell_flat, h);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int smashx_hyper_info(const smashx_plan* p, int info[4], float device_ms[2]) {
+    if (!p || !info || !device_ms) return fail(SMASHX_E_ARG, "null argument");
+    const smashx_plan::Hyper& H = p->hyp;
+    info[0] = H.nd; info[1] = H.nh; info[2] = H.nchain; info[3] = H.span;
+    device_ms[0] = H.map_ms; device_ms[1] = H.grad_ms;
     return 0;
 }
 

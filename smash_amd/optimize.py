@@ -35,16 +35,18 @@ class _Stop(Exception):
     pass
 
 
-def _lbfgsb_native(fg, x0, m, factr, pgtol, maxiter, maxfun, callback):
+def _lbfgsb_native(fg, x0, m, factr, pgtol, maxiter, maxfun, callback, lower=None, upper=None):
     """The library's own L-BFGS-B (include/smashx.h smashx_lbfgsb_*: written from Byrd-Lu-Nocedal-Zhu 1995 / Morales-Nocedal 2011 /
     More'-Thuente, threaded host C++) on the box [0, 1]^n.  No scipy in the loop.  Same method, parameters and stopping tests as the
     lbfgsb.f the reference calls; on test problems its iterates agree with scipy's build of that code to 1e-15 per iteration
-    (tests/test_cabi_cpu.py).  Returns (x, f, info) like _lbfgsb_scipy."""
+    (tests/test_cabi_cpu.py).  lower / upper: other bounds than the box (+-inf = none on that side).  Returns (x, f, info) like
+    _lbfgsb_scipy."""
     import ctypes as C
     from . import _lib
     L = _lib.lib()
     n = x0.size
-    lo, up = np.zeros(n, np.float64), np.ones(n, np.float64)
+    lo = np.zeros(n, np.float64) if lower is None else np.ascontiguousarray(lower, np.float64)
+    up = np.ones(n, np.float64) if upper is None else np.ascontiguousarray(upper, np.float64)
     h = C.c_void_p()
     _lib.check(L.smashx_lbfgsb_create(n, m, lo.ctypes.data, up.ctypes.data, factr, pgtol, C.byref(h)))
     try:
@@ -418,4 +420,163 @@ def optimize_lbfgsb(setup, mesh, input_data, parameters, states, output, verbose
         hist["final_cost"] = whole_cost()
     finally:
         o.denormalize_forward = was
+    return hist
+
+
+# ---- regionalisation: mw_optimize::optimize_hyper_lbfgsb (mw_optimize.f90:779-1177) ---------------------------------------------------
+def _logf(x):
+    """logf of the C library, which the reference's compiled code calls (numpy's float32 log is another implementation)"""
+    import ctypes as C
+    import ctypes.util
+    lm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    lm.logf.restype, lm.logf.argtypes = C.c_float, [C.c_float]
+    return np.float32(lm.logf(C.c_float(float(x))))
+
+
+def hyper_problem_initialise(setup, mesh, parameters, states):
+    """problem_initialise_hyper_lbfgsb + var_to_control_hyper_lbfgsb (mw_optimize.f90:1001-1135).  Returns (hyper_parameters,
+    hyper_states, x0, l, u, nbd): the first row of every column is the inverse sigmoid of the field at maxloc(active_cell) (fp32,
+    both operands floored at 1e-8), every other coefficient 0; the exponents of a flagged field under hyper-polynomial start at 1 with
+    bounds [0.5, 2] (nbd = 2), everything else is unbounded (nbd = 0, l = u = 0 as the reference leaves them).  The control is the
+    flagged columns, parameters before states."""
+    from .types import Hyper_ParametersDT, Hyper_StatesDT
+    o = setup.optimize
+    nh = int(o.nhyper)
+    flat = int(np.argmax(np.asarray(mesh.active_cell).reshape(-1, order="F")))        # maxloc: the first maximum in array element order
+    r, c = flat % mesh.nrow, flat // mesh.nrow
+    f32 = np.float32
+    H = np.zeros((nh, len(PARAM_NAMES) + len(STATE_NAMES)), f32, order="F")
+    vals = [getattr(parameters, k)[r, c] for k in PARAM_NAMES] + [getattr(states, k)[r, c] for k in STATE_NAMES]
+    lb = np.concatenate([np.asarray(o.lb_parameters, f32), np.asarray(o.lb_states, f32)])
+    ub = np.concatenate([np.asarray(o.ub_parameters, f32), np.asarray(o.ub_states, f32)])
+    for i, v in enumerate(vals):
+        v = f32(v)
+        H[0, i] = _logf(max(f32(1e-8), f32(v - lb[i])) / max(f32(1e-8), f32(ub[i] - v)))
+    optim = np.concatenate([np.asarray(o.optim_parameters), np.asarray(o.optim_states)]) > 0
+    n = int(np.count_nonzero(optim)) * nh
+    l, u, nbd = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.int32)
+    k = 0
+    for i in np.flatnonzero(optim):
+        if o.mapping == "hyper-polynomial":
+            for j in range(2, nh, 2):                       # rows 3, 5, ... of the column (1-based): the exponents
+                H[j, i] = 1.0
+                nbd[k + j], l[k + j], u[k + j] = 2, 0.5, 2.0
+        k += nh
+    HP, HS = Hyper_ParametersDT(setup), Hyper_StatesDT(setup)
+    HP.set_matrix(H[:, :len(PARAM_NAMES)])
+    HS.set_matrix(H[:, len(PARAM_NAMES):])
+    x0 = np.concatenate([H[:, i].astype(np.float64) for i in np.flatnonzero(optim)]) if n else np.zeros(0, np.float64)
+    return HP, HS, x0, l, u, nbd
+
+
+def optimize_hyper_lbfgsb(setup, mesh, input_data, parameters, states, output, verbose=False, device_map=True, evaluate=None):
+    """Mirror of mw_optimize::optimize_hyper_lbfgsb (mw_optimize.f90:779-958): the coefficients of the descriptor -> field maps
+    (setup.optimize.mapping = "hyper-linear" | "hyper-polynomial", nhyper rows per field) calibrated by L-BFGS-B with m = 10,
+    factr = 1e6, pgtol = 1e-12, the bounds of hyper_problem_initialise, stopped at setup.optimize.maxiter iterations or when
+    |proj g| <= 1e-10 (1 + |f|).  ALL 24 fields are mapped; the flagged ones form the control, parameters before states.  The
+    descriptors are normalised by their whole-grid minimum and maximum for the calibration and put back afterwards (exactly as they
+    were; the reference recomputes them from the normalised values).  In place like the reference: parameters / states come back as
+    the mapped fields of the calibrated coefficients over the WHOLE grid, output holds the final hyper_forward run.
+
+    device_map = True: every evaluation is hyper_upload -> adjoint sweep -> hyper_gradient on the device (include/smashx_hyper.h) --
+    two small matrices go up, two come back; False: the host composition smash_amd.hyper_forward_b (planes over PCIe, the maps of
+    sx_hyper.cpp), which computes the same numbers bit for bit.  evaluate(hyper_parameters, hyper_states) -> (cost, hyper_parameters_b
+    matrix, hyper_states_b matrix) replaces both, and the final run with them (the loop can then be driven without a GPU; the
+    descriptors it sees in input_data are the normalised ones).
+
+    Returns the history dict of optimize_lbfgsb (cost per iterate, nfg, task, final_cost) plus cost_initial, x0 / l / u / nbd and
+    the final matrices hyper_parameters (nhyper, 16) / hyper_states (nhyper, 8)."""
+    from .solver import _hyper_to_fields, _plain, hyper_forward, hyper_forward_b
+    o = setup.optimize
+    if o.mapping not in ("hyper-linear", "hyper-polynomial"):
+        raise ValueError(f"setup.optimize.mapping = {o.mapping!r}: hyper-linear or hyper-polynomial expected")
+    maxiter = int(getattr(o, "maxiter", 100))
+    optim = np.concatenate([np.asarray(o.optim_parameters), np.asarray(o.optim_states)]) > 0
+    if not optim.any():
+        raise ValueError("nothing to optimise: optim_parameters / optim_states are all zero")
+    nh, npar = int(o.nhyper), len(PARAM_NAMES)
+
+    # normalize_descriptor_hyper_lbfgsb (:960-980), fp32
+    desc0 = input_data.descriptor
+    desc = np.asfortranarray(desc0, dtype=np.float32).copy(order="F")
+    for i in range(desc.shape[2]):
+        lo, hi = desc[:, :, i].min(), desc[:, :, i].max()
+        desc[:, :, i] = (desc[:, :, i] - lo) / (hi - lo)
+    input_data.descriptor = desc
+    try:
+        HP, HS, x0, l, u, nbd = hyper_problem_initialise(setup, mesh, parameters, states)
+        hist = {"cost": [], "nfg": 0, "x0": x0.copy(), "l": l, "u": u, "nbd": nbd}
+        last = {}
+        injected = evaluate is not None
+        if not injected and device_map:
+            sol = _solver_for(_plain(setup), mesh, input_data)
+            sol.set_hyper_descriptors(o.mapping, desc)
+
+            def evaluate(hp, hs):
+                sol.hyper_upload(hp, hs)
+                sol.sweep(True, 1.0)
+                cost = sol.cost_and_qsim(output)
+                hpb, hsb = sol.hyper_gradient()
+                return cost, hpb, hsb
+        elif not injected:
+            par_b, sta_b = parameters.copy(), states.copy()
+
+            def evaluate(hp, hs):
+                HPb, HSb = HP.copy(), HS.copy()
+                cost = hyper_forward_b(setup, mesh, input_data, parameters, par_b, HP, HPb, HP, states, sta_b, HS, HSb, HS, output, None,
+                                       np.float32(0), np.float32(1))
+                return cost, HPb.matrix(), HSb.matrix()
+
+        def to_var(x):
+            # control_to_var_hyper_lbfgsb (:1137-1177): real(x(k), sp) into the flagged columns
+            M = np.concatenate([HP.matrix(), HS.matrix()], axis=1)
+            for j, i in enumerate(np.flatnonzero(optim)):
+                M[:, i] = np.asarray(x[j * nh:(j + 1) * nh], np.float64).astype(np.float32)
+            HP.set_matrix(M[:, :npar])
+            HS.set_matrix(M[:, npar:])
+
+        def fg(x):
+            to_var(x)
+            cost, hpb, hsb = evaluate(HP.matrix(), HS.matrix())
+            G = np.concatenate([np.asarray(hpb, np.float32), np.asarray(hsb, np.float32)], axis=1)
+            g = np.concatenate([G[:, i].astype(np.float64) for i in np.flatnonzero(optim)])
+            hist["nfg"] += 1
+            last["f"], last["g"] = float(np.float32(cost)), g
+            if hist["nfg"] == 1:
+                hist["cost_initial"] = last["f"]
+            return last["f"], g
+
+        def cb(xk, pg=None):
+            hist["cost"].append(last["f"])
+            if verbose:
+                print(f"    At iterate {len(hist['cost']):3d}    nfg = {hist['nfg']:5d}    J = {last['f']:14.6f}")
+            if pg is not None and pg <= 1e-10 * (1.0 + abs(last["f"])):
+                last["x"] = xk.copy()
+                raise _Stop
+
+        cb.wants_pg = True
+        lower = np.where(nbd == 2, l, -np.inf)
+        upper = np.where(nbd == 2, u, np.inf)
+        try:
+            x, f, info = _lbfgsb_native(fg, x0, 10, 1e6, 1e-12, maxiter, 1 << 30, cb, lower, upper)
+            hist["task"] = str(info.get("task", ""))
+        except _Stop:
+            x = last["x"]
+            hist["task"] = "STOP: THE PROJECTED GRADIENT IS SUFFICIENTLY SMALL"
+        to_var(x)
+        # the final hyper_forward (:950-954); the caller's planes are then mapped over the whole grid, inactive cells included, as
+        # hyper_parameters_to_parameters / hyper_states_to_states leave them
+        if injected:
+            hist["final_cost"] = float(np.float32(evaluate(HP.matrix(), HS.matrix())[0]))
+        elif device_map:
+            sol.hyper_upload(HP.matrix(), HS.matrix())
+            sol.sweep(False)
+            hist["final_cost"] = float(np.float32(sol.download(False, None, None, output)))
+        else:
+            hist["final_cost"] = float(np.float32(hyper_forward(setup, mesh, input_data, parameters, HP, HP, states, HS, HS, output,
+                                                                np.float32(0))))
+        _hyper_to_fields(setup, mesh, input_data, parameters, HP, states, HS)
+        hist["hyper_parameters"], hist["hyper_states"] = HP.matrix(), HS.matrix()
+    finally:
+        input_data.descriptor = desc0
     return hist

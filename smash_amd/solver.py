@@ -476,6 +476,80 @@ class Solver:
         _lib.check(_lib.lib().smashx_prcp_indices(self._h, _ptr(dst), _ptr(out)))
         return out
 
+    # -- hyper maps on the device (include/smashx_hyper.h) -------------------------------------------
+    def set_hyper_descriptors(self, mapping, descriptor):
+        """input_data.descriptor (nrow, ncol, nd) float32 Fortran order and the mapping ("hyper-linear" / "hyper-polynomial") into HBM
+        (smashx_hyper_set_descriptors); handing over what the plan already holds moves nothing.  descriptor = None drops them."""
+        code, nd, desc = check_hyper_descriptors(self.nrow, self.ncol, mapping, descriptor)
+        _lib.check(_lib.lib().smashx_hyper_set_descriptors(self._h, code, nd, _ptr(desc)))
+        self._hyper_nh = None if desc is None else (1 + 2 * nd if code == HYPER["hyper-polynomial"] else 1 + nd)
+
+    def hyper_upload(self, hyper_parameters, hyper_states):
+        """The forward map on the device, in place of upload() in front of sweep(): hyper_parameters (nhyper, 16) and hyper_states
+        (nhyper, 8), float32 Fortran order (Hyper_ParametersDT.matrix())."""
+        hp, hs = check_hyper_matrices(getattr(self, "_hyper_nh", None), hyper_parameters, hyper_states)
+        _lib.check(_lib.lib().smashx_hyper_upload(self._h, _ptr(hp), _ptr(hs)))
+
+    def hyper_gradient(self, hyper_parameters_b=None, hyper_states_b=None):
+        """After an adjoint sweep: (hyper_parameters_b (nhyper, 16), hyper_states_b (nhyper, 8)), the arrays given -- overwritten --
+        or new ones."""
+        nh = getattr(self, "_hyper_nh", None)
+        if hyper_parameters_b is None and nh is not None:
+            hyper_parameters_b = np.zeros((nh, len(PARAM_NAMES)), np.float32, order="F")
+        if hyper_states_b is None and nh is not None:
+            hyper_states_b = np.zeros((nh, len(STATE_NAMES)), np.float32, order="F")
+        hpb, hsb = check_hyper_matrices(nh, hyper_parameters_b, hyper_states_b, writeable=True)
+        _lib.check(_lib.lib().smashx_hyper_gradient(self._h, _ptr(hpb), _ptr(hsb)))
+        return hpb, hsb
+
+    def hyper_fields(self, parameters=None, states=None):
+        """The mapped fields of the last hyper_upload into the planes of parameters / states (either may be None): active cells are
+        written, the others keep their values."""
+        P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
+        S, k2 = _pack(states, STATE_NAMES, _lib.States)
+        for keep in (k1, k2):
+            for a in keep:
+                if a.shape != (self.nrow, self.ncol) or not a.flags.writeable:
+                    raise _lib.SmashxError(_lib.E_ARG, f"hyper_fields: every plane must be a writeable ({self.nrow}, {self.ncol}) array")
+        _lib.check(_lib.lib().smashx_hyper_fields(self._h, C.byref(P), C.byref(S)))
+
+    def hyper_info(self):
+        """{nd, nhyper, chains, span, map_ms, gradient_ms} of the last hyper_upload / hyper_gradient on this plan (smashx_hyper_info)."""
+        info, ms = (C.c_int * 4)(), (C.c_float * 2)()
+        _lib.check(_lib.lib().smashx_hyper_info(self._h, info, ms))
+        return {"nd": info[0], "nhyper": info[1], "chains": info[2], "span": info[3], "map_ms": float(ms[0]), "gradient_ms": float(ms[1])}
+
+
+def check_hyper_descriptors(nrow, ncol, mapping, descriptor):
+    """Argument checks of set_hyper_descriptors, before anything reaches the C call (an array of another shape, type or order would be
+    read out of bounds or scrambled).  Returns (mapping code, nd, descriptor) ready for the call -- descriptor None (drop) gives
+    (code, 1, None); raises SmashxError(E_ARG)."""
+    def bad(msg):
+        return _lib.SmashxError(_lib.E_ARG, "hyper descriptors: " + msg)
+    if mapping not in HYPER:
+        raise bad(f"mapping = {mapping!r}: hyper-linear or hyper-polynomial expected")
+    if descriptor is None:
+        return HYPER[mapping], 1, None
+    if (not isinstance(descriptor, np.ndarray) or descriptor.ndim != 3 or descriptor.shape[:2] != (nrow, ncol)
+            or descriptor.dtype != np.float32 or not descriptor.flags.f_contiguous):
+        raise bad(f"descriptor must be a Fortran-ordered float32 array of shape ({nrow}, {ncol}, nd)")
+    return HYPER[mapping], int(descriptor.shape[2]), descriptor
+
+
+def check_hyper_matrices(nhyper, hyper_parameters, hyper_states, writeable=False):
+    """Argument checks of hyper_upload / hyper_gradient: (nhyper, 16) and (nhyper, 8) float32 Fortran-ordered matrices, nhyper as the
+    descriptors the plan holds give it (None: none set).  Returns the two arrays; raises SmashxError(E_STATE) without descriptors and
+    SmashxError(E_ARG) for everything else."""
+    def bad(msg):
+        return _lib.SmashxError(_lib.E_ARG, "hyper matrices: " + msg)
+    if nhyper is None:
+        raise _lib.SmashxError(_lib.E_STATE, "hyper matrices: no descriptors set (set_hyper_descriptors)")
+    for name, a, nf in (("hyper_parameters", hyper_parameters, len(PARAM_NAMES)), ("hyper_states", hyper_states, len(STATE_NAMES))):
+        if (not isinstance(a, np.ndarray) or a.shape != (nhyper, nf) or a.dtype != np.float32 or not a.flags.f_contiguous
+                or (writeable and not a.flags.writeable)):
+            raise bad(f"{name} must be a {'writeable ' if writeable else ''}Fortran-ordered float32 array of shape ({nhyper}, {nf})")
+    return hyper_parameters, hyper_states
+
 
 # fields each structure reads, stacked md_constant order 1..24 (include/smashx.h: parameters 1..16, states 17..24)
 FIELD_NAMES = tuple(PARAM_NAMES) + tuple(STATE_NAMES)
