@@ -435,6 +435,8 @@ int smashx_lbfgsb_destroy(smashx_lbfgsb* opt);
 #include "smashx_signature.h"
 /* ---- hyper maps on the device (the control vector of optimize_hyper_lbfgsb): declared in smashx_hyper.h, likewise ------------------------ */
 #include "smashx_hyper.h"
+/* ---- the ANN regionalisation on the device (ann_optimize) and the same network on the host: declared in smashx_ann.h, likewise ---------- */
+#include "smashx_ann.h"
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """ctypes view of include/smashx.h, declared once: the header's constants, one class per struct (STRUCTS), one prototype per function
-(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h, PRCP_PROTOTYPES for include/smashx_prcp.h, SIGNATURE_PROTOTYPES for include/smashx_signature.h and HYPER_DEVICE_PROTOTYPES for include/smashx_hyper.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
+(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h, PRCP_PROTOTYPES for include/smashx_prcp.h, SIGNATURE_PROTOTYPES for include/smashx_signature.h HYPER_DEVICE_PROTOTYPES for include/smashx_hyper.h and ANN_PROTOTYPES for include/smashx_ann.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
 PROTOTYPES.  Loading fails loudly when libsmashx.so is missing: there is no Python / CPU implementation of the solver behind this
 module."""
 from __future__ import annotations
@@ -191,6 +191,25 @@ HYPER_DEVICE_PROTOTYPES = {
     "smashx_hyper_info": (_int, [ptr, ptr, ptr]),
 }
 HYPER_DEVICE_SYMBOLS = list(HYPER_DEVICE_PROTOTYPES)
+# ---- every function of include/smashx_ann.h (the ANN regionalisation on the device and the same network on the host, which smashx.h
+# includes as well), the same way; tests/test_ann_cpu.py reads that header and compares.  ANN_LAYER: the header's enum.
+ANN_LAYER = {"dense": 1, "relu": 2, "leaky_relu": 3, "elu": 4, "selu": 5, "sigmoid": 6, "tanh": 7, "scale": 8,       # SMASHX_ANN_DENSE ...
+             "softplus": 9, "softmax": 10, "dropout": 11}
+_graph = [_int, _int, ptr, ptr, _int]             # nd, nlayers, kind, width, ncv
+ANN_PROTOTYPES = {
+    "smashx_ann_set_descriptors": (_int, [ptr, _int, ptr]),
+    "smashx_ann_set_net": (_int, [ptr, _int, ptr, ptr, _int, ptr, ptr, ptr]),
+    "smashx_ann_upload": (_int, [ptr, ptr]),
+    "smashx_ann_gradient": (_int, [ptr, ptr]),
+    "smashx_ann_fields": (_int, [ptr, _par, _sta]),
+    "smashx_ann_info": (_int, [ptr, ptr, ptr]),
+    "smashx_ann_host_nweights": (_int, _graph),
+    "smashx_ann_host_forward": (_int, _graph + [ptr, ptr, ptr, _long, ptr, ptr]),
+    "smashx_ann_host_gradient": (_int, _graph + [ptr, ptr, ptr, _long, ptr, ptr, ptr]),
+    "smashx_ann_host_activation": (_int, [_int, _long, ptr, ptr, ptr]),
+    "smashx_ann_host_exp": (_int, [_long, ptr, ptr]),
+}
+ANN_SYMBOLS = list(ANN_PROTOTYPES)
 
 
 class SmashxError(RuntimeError):
@@ -211,7 +230,7 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: build the HIP library first (__graft_entry__.build()); "
                               "smash_amd has no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()) + list(SIGNATURE_PROTOTYPES.items()) + list(HYPER_DEVICE_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()) + list(SIGNATURE_PROTOTYPES.items()) + list(HYPER_DEVICE_PROTOTYPES.items()) + list(ANN_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         # the structs above mirror include/smashx.h by hand: refuse a library built from another layout (a stale .so would have

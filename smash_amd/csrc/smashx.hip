@@ -26,6 +26,8 @@
 #include "sx_prcpindices.h"
 #include "sx_hypermap.h"
 #include "sx_hyperhost.h"
+#include "sx_annmap.h"
+#include "sx_annhost.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -464,6 +466,24 @@ struct smashx_plan {
         int nchain = 0, span = 0;
         float map_ms = 0.f, grad_ms = 0.f;
     } hyp;
+    // the ANN regionalisation on the device (smashx_ann_*, sx_annmap.h): its own descriptors in plan-cell order with the host copy they
+    // are compared with, the graph, the packed weights, cell vectors for the control fields without a slot, the staging rows of a span
+    struct Ann {
+        bool have_desc = false, have_net = false, mapped = false;    // mapped: a smashx_ann_upload has run with the descriptors and the net held
+        int nd = 0;
+        std::vector<float> h_desc;               // [nd][n], as gathered
+        float* d_desc = nullptr; size_t desc_cap = 0;
+        int* d_order = nullptr;
+        SxAnnNet net{};
+        int field[SX_ANN_MAXCV] = {0};
+        double* d_w = nullptr; size_t w_cap = 0;
+        float* d_extra = nullptr; size_t extra_cap = 0;
+        double* d_terms = nullptr; size_t terms_cap = 0;
+        double* d_sums = nullptr; size_t sums_cap = 0;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        int span = 0;
+        float map_ms = 0.f, grad_ms = 0.f;
+    } ann;
     struct Ens {
         bool tables = false;
         int nlevels = 0; std::vector<int> level_begin;
@@ -1161,6 +1181,7 @@ int smashx_plan_destroy(smashx_plan* p) {
     if (p->ens.ev_a) (void)hipEventDestroy(p->ens.ev_a);
     if (p->ens.ev_b) (void)hipEventDestroy(p->ens.ev_b);
     for (hipEvent_t e : p->hyp.ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : p->ann.ev) if (e) (void)hipEventDestroy(e);
     delete p;
     return 0;
 }
@@ -2985,6 +3006,246 @@ int smashx_hyper_info(const smashx_plan* p, int info[4], float device_ms[2]) {
     const smashx_plan::Hyper& H = p->hyp;
     info[0] = H.nd; info[1] = H.nh; info[2] = H.nchain; info[3] = H.span;
     device_ms[0] = H.map_ms; device_ms[1] = H.grad_ms;
+    return 0;
+}
+
+// ---- the ANN regionalisation on the device (include/smashx_ann.h, sx_annmap.h) and its host twin (sx_annhost.h) ---------------------------
+namespace {
+extern "C++" {
+template <class T> int ann_grow(smashx_plan* p, T** buf, size_t* cap, size_t need) {
+    if (*cap >= need) return 0;
+    if (*buf) p->dfree(*buf);
+    *buf = nullptr; *cap = 0;
+    int rc = p->dmalloc(buf, need); if (rc) return rc;
+    *cap = need;
+    return 0;
+}
+}
+// what smashx_ann_upload / _gradient / _fields refuse before they look at their own state, in the order of the header's table
+int ann_refusal(const smashx_plan* p, const char* who) {
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": a tiled plan (the weight gradient is a whole-grid sum)");
+    const smashx_plan::Ann& A = p->ann;
+    if (!A.have_desc) return fail(SMASHX_E_STATE, std::string(who) + ": no descriptors set (smashx_ann_set_descriptors)");
+    if (!A.have_net) return fail(SMASHX_E_STATE, std::string(who) + ": no net set (smashx_ann_set_net)");
+    if (A.nd != A.net.nd) return fail(SMASHX_E_STATE, std::string(who) + ": the net's input width is not the number of descriptors");
+    if (!p->uploaded) return fail(SMASHX_E_STATE, std::string(who) + ": no smashx_upload of the background fields");
+    // compute_jreg reads the planes smashx_upload placed beside the background, not the mapped ones, and its gradient is added at
+    // download, behind the cell gradients the adjoint map reads
+    if (p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": a regulariser (njr > 0: the cost's jreg term does not see the mapped fields)");
+    return 0;
+}
+// the control fields as one launch: a field with a slot goes to its cell vectors and plane, any other to a cell vector of its own
+SxHmFields ann_fields_of(smashx_plan* p, bool grad) {
+    smashx_plan::Ann& A = p->ann;
+    SxHmFields F{};
+    F.nf = A.net.ncv;
+    int extra = 0;
+    for (int e = 0; e < F.nf; ++e) {
+        const int f = A.field[e], s = sx_field_slot(p->st, f);
+        F.field[e] = f;
+        if (s >= 0) {
+            const SlotVecs V = slot_vecs(p, s);
+            F.val[e] = V.val; F.start[e] = V.start != V.val ? V.start : nullptr; F.full[e] = p->d_full[f];
+            F.grad[e] = grad ? V.grad : nullptr;
+        } else {
+            F.val[e] = A.d_extra + (size_t)extra++ * std::max(p->n, 1);
+        }
+    }
+    return F;
+}
+int ann_extra_count(const smashx_plan* p) {
+    int extra = 0;
+    for (int e = 0; e < p->ann.net.ncv; ++e) if (sx_field_slot(p->st, p->ann.field[e]) < 0) ++extra;
+    return extra;
+}
+int ann_events(smashx_plan* p) {
+    for (hipEvent_t& e : p->ann.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    return 0;
+}
+// the LDS of a workgroup of the map / terms kernels; above 64 KiB a kernel has to be told
+int ann_lds(const smashx_plan* p, size_t* lds) {
+    *lds = (size_t)p->ann.net.nslots * SX_ANN_BLOCK * sizeof(double);
+    if (*lds > 64 * 1024) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sx_k_ann_map), hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sx_k_ann_terms), hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds));
+    }
+    return 0;
+}
+int ann_host_net(int nd, int nlayers, const int* kind, const int* width, int ncv, const double* lower, const double* upper, SxAnnNet* N) {
+    const char* why = "";
+    const int rc = sx_annh_build(nd, nlayers, kind, width, ncv, lower, upper, N, &why);
+    return rc ? fail(rc, std::string("ann graph: ") + why) : 0;
+}
+}  // namespace
+
+int smashx_ann_set_descriptors(smashx_plan* p, int nd, const float* descriptor) {
+    if (!p || !descriptor) return fail(SMASHX_E_ARG, "smashx_ann_set_descriptors: null argument");
+    if (nd < 1) return fail(SMASHX_E_ARG, "smashx_ann_set_descriptors: nd < 1");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_ann_set_descriptors: a tiled plan (the weight gradient is a whole-grid sum)");
+    smashx_plan::Ann& A = p->ann;
+    int rc = set_device(p); if (rc) return rc;
+    std::vector<float> g;
+    sx_hh_gather(descriptor, nd, (size_t)p->n2, p->sch.cell_flat, g);
+    if (!A.d_order && (rc = p->upload_vec(&A.d_order, sx_hh_order(p->sch.cell_flat)))) return rc;
+    const bool same = A.have_desc && A.nd == nd && g.size() == A.h_desc.size() &&
+                      std::memcmp(g.data(), A.h_desc.data(), g.size() * 4) == 0;      // (bits: a NaN equals itself here)
+    if (!same) {
+        if ((rc = ann_grow(p, &A.d_desc, &A.desc_cap, std::max<size_t>(g.size(), 1)))) return rc;
+        if (!g.empty()) HIPCHK(hipMemcpy(A.d_desc, g.data(), g.size() * 4, hipMemcpyHostToDevice));
+        A.h_desc.swap(g);
+        A.mapped = false;
+    }
+    A.nd = nd; A.have_desc = true;
+    return 0;
+}
+
+int smashx_ann_set_net(smashx_plan* p, int nlayers, const int* kind, const int* width, int ncv, const int* field,
+                       const double* lower, const double* upper) {
+    if (!p || !kind || !width || !field) return fail(SMASHX_E_ARG, "smashx_ann_set_net: null argument");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_ann_set_net: a tiled plan (the weight gradient is a whole-grid sum)");
+    if (ncv < 1) return fail(SMASHX_E_ARG, "smashx_ann_set_net: ncv < 1");
+    if (ncv > SX_ANN_MAXCV) return fail(SMASHX_E_UNSUPPORTED, "smashx_ann_set_net: ncv > 24");
+    for (int e = 0; e < ncv; ++e) {
+        if (field[e] < 0 || field[e] >= SX_NFIELDS) return fail(SMASHX_E_ARG, "smashx_ann_set_net: field outside 0 .. 23");
+        for (int q = 0; q < e; ++q) if (field[q] == field[e]) return fail(SMASHX_E_ARG, "smashx_ann_set_net: a field named twice");
+    }
+    // the net's input width is the number of descriptors the plan holds.  Without descriptors the call is refused with SMASHX_E_STATE; the
+    // graph is still built first, with a stand-in width of 1, only so that a graph that is none ranks ahead of that (SMASHX_E_ARG)
+    smashx_plan::Ann& A = p->ann;
+    SxAnnNet N{};
+    int rc = ann_host_net(A.have_desc ? A.nd : 1, nlayers, kind, width, ncv, lower, upper, &N); if (rc) return rc;
+    if (!A.have_desc) return fail(SMASHX_E_STATE, "smashx_ann_set_net: no descriptors set (their number is the net's input width)");
+    if (const char* why = sx_annh_device_refusal(N)) return fail(SMASHX_E_UNSUPPORTED, std::string("smashx_ann_set_net: ") + why);
+    A.net = N;
+    for (int e = 0; e < ncv; ++e) A.field[e] = field[e];
+    A.have_net = true; A.mapped = false;
+    return 0;
+}
+
+int smashx_ann_upload(smashx_plan* p, const double* weights) {
+    if (!p || !weights) return fail(SMASHX_E_ARG, "smashx_ann_upload: null argument");
+    int rc = ann_refusal(p, "smashx_ann_upload"); if (rc) return rc;
+    if ((rc = set_device(p))) return rc;
+    smashx_plan::Ann& A = p->ann;
+    size_t lds = 0;
+    if ((rc = ann_grow(p, &A.d_w, &A.w_cap, (size_t)A.net.nw))) return rc;
+    if ((rc = ann_grow(p, &A.d_extra, &A.extra_cap, (size_t)std::max(ann_extra_count(p), 1) * std::max(p->n, 1)))) return rc;
+    if ((rc = ann_events(p)) || (rc = ann_lds(p, &lds))) return rc;
+    HIPCHK(hipMemcpyAsync(A.d_w, weights, (size_t)A.net.nw * 8, hipMemcpyHostToDevice, p->stream));
+    const SxHmFields F = ann_fields_of(p, false);
+    const dim3 b(SX_ANN_BLOCK), g((p->n + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK), gk((p->n + 255) / 256);
+    HIPCHK(hipEventRecord(A.ev[0], p->stream));
+    if (p->n > 0) hipLaunchKernelGGL(sx_k_ann_map, g, b, lds, p->stream, A.net, F, A.d_w, A.d_desc, p->d_cell_flat, p->n);
+    HIPCHK(hipEventRecord(A.ev[1], p->stream));
+    hipLaunchKernelGGL(sx_k_prep_routing, gk, dim3(256), 0, p->stream, p->A);
+    p->jr_ready = false;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventElapsedTime(&A.map_ms, A.ev[0], A.ev[1]));
+    p->last_adjoint = 0;           // a gradient belongs to a sweep behind THIS upload
+    A.mapped = true;
+    return 0;
+}
+
+int smashx_ann_gradient(smashx_plan* p, double* weights_b) {
+    if (!p || !weights_b) return fail(SMASHX_E_ARG, "smashx_ann_gradient: null argument");
+    int rc = ann_refusal(p, "smashx_ann_gradient"); if (rc) return rc;
+    smashx_plan::Ann& A = p->ann;
+    if (!A.mapped) return fail(SMASHX_E_STATE, "smashx_ann_gradient: no smashx_ann_upload with the descriptors and the net the plan holds");
+    if (!(p->adj_ready && p->last_adjoint)) return fail(SMASHX_E_STATE, "smashx_ann_gradient: no adjoint sweep behind the smashx_ann_upload");
+    if ((rc = set_device(p))) return rc;
+    const int nw = A.net.nw;
+    // cells per span, whole blocks: from the environment, else what keeps the staging rows at SX_ANN_STAGE_BYTES
+    long span = ens_env("SMASHX_ANN_SPAN");
+    if (span <= 0) span = (long)std::max<size_t>(16, SX_ANN_STAGE_BYTES / ((size_t)nw * 8)) * SX_ANN_BLOCK;
+    span = (span + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK * SX_ANN_BLOCK;
+    span = std::min<long>(span, (std::max(p->n, 1) + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK * SX_ANN_BLOCK);
+    size_t lds = 0;
+    if ((rc = ann_grow(p, &A.d_terms, &A.terms_cap, (size_t)(span / SX_ANN_BLOCK) * nw))) return rc;
+    if ((rc = ann_grow(p, &A.d_sums, &A.sums_cap, (size_t)nw))) return rc;
+    if ((rc = ann_events(p)) || (rc = ann_lds(p, &lds))) return rc;
+    A.span = (int)span;
+    const SxHmFields F = ann_fields_of(p, true);
+    HIPCHK(hipEventRecord(A.ev[2], p->stream));
+    HIPCHK(hipMemsetAsync(A.d_sums, 0, (size_t)nw * 8, p->stream));
+    for (long c0 = 0; c0 < p->n; c0 += span) {
+        const int ns = (int)std::min<long>(span, p->n - c0);
+        const int nb = (ns + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK;
+        hipLaunchKernelGGL(sx_k_ann_terms, dim3(nb), dim3(SX_ANN_BLOCK), lds, p->stream, A.net, F, A.d_w, A.d_desc, A.d_order, p->n, (int)c0, ns, A.d_terms);
+        hipLaunchKernelGGL(sx_k_ann_walk, dim3((nw + 63) / 64), dim3(64), 0, p->stream, A.d_terms, nb, nw, A.d_sums);
+    }
+    HIPCHK(hipEventRecord(A.ev[3], p->stream));
+    std::vector<double> sums((size_t)nw);
+    HIPCHK(hipMemcpyAsync(sums.data(), A.d_sums, (size_t)nw * 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventElapsedTime(&A.grad_ms, A.ev[2], A.ev[3]));
+    std::memcpy(weights_b, sums.data(), (size_t)nw * 8);
+    return 0;
+}
+
+int smashx_ann_fields(smashx_plan* p, smashx_parameters* params, smashx_states* states) {
+    if (!p) return fail(SMASHX_E_ARG, "null plan");
+    int rc = ann_refusal(p, "smashx_ann_fields"); if (rc) return rc;
+    smashx_plan::Ann& A = p->ann;
+    if (!A.mapped) return fail(SMASHX_E_STATE, "smashx_ann_fields: no smashx_ann_upload with the descriptors and the net the plan holds");
+    if ((rc = set_device(p))) return rc;
+    const SxHmFields F = ann_fields_of(p, false);
+    std::vector<float> cellv((size_t)p->n);
+    for (int e = 0; e < F.nf; ++e) {
+        float* const h = host_plane(params, states, F.field[e]);
+        if (!h) continue;
+        const float* src = F.start[e] ? F.start[e] : F.val[e];         // what the upload stored: a state's starting values
+        HIPCHK(hipMemcpyAsync(cellv.data(), src, (size_t)p->n * 4, hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        sx_hh_scatter(cellv.data(), p->sch.cell_flat, h);
+    }
+    return 0;
+}
+
+int smashx_ann_info(const smashx_plan* p, int info[4], float device_ms[2]) {
+    if (!p || !info || !device_ms) return fail(SMASHX_E_ARG, "null argument");
+    const smashx_plan::Ann& A = p->ann;
+    info[0] = A.nd; info[1] = A.have_net ? A.net.nw : 0; info[2] = A.span; info[3] = A.have_net ? A.net.nslots * SX_ANN_BLOCK * 8 : 0;
+    device_ms[0] = A.map_ms; device_ms[1] = A.grad_ms;
+    return 0;
+}
+
+int smashx_ann_host_nweights(int nd, int nlayers, const int* kind, const int* width, int ncv) {
+    SxAnnNet N{};
+    const std::vector<double> zero((size_t)std::max(ncv, 1), 0.0);
+    const int rc = ann_host_net(nd, nlayers, kind, width, ncv, zero.data(), zero.data(), &N);
+    return rc ? rc : N.nw;
+}
+int smashx_ann_host_forward(int nd, int nlayers, const int* kind, const int* width, int ncv, const double* lower, const double* upper,
+                            const double* weights, long n, const float* x, float* y) {
+    SxAnnNet N{};
+    int rc = ann_host_net(nd, nlayers, kind, width, ncv, lower, upper, &N); if (rc) return rc;
+    if (n < 0 || !weights || (n > 0 && (!x || !y))) return fail(SMASHX_E_ARG, "smashx_ann_host_forward: null argument");
+    sx_annh_forward(N, weights, (size_t)n, x, (size_t)nd, 1, y);
+    return 0;
+}
+int smashx_ann_host_gradient(int nd, int nlayers, const int* kind, const int* width, int ncv, const double* lower, const double* upper,
+                             const double* weights, long n, const float* x, const float* loss_grad, double* weights_b) {
+    SxAnnNet N{};
+    int rc = ann_host_net(nd, nlayers, kind, width, ncv, lower, upper, &N); if (rc) return rc;
+    if (n < 0 || !weights || !weights_b || (n > 0 && (!x || !loss_grad))) return fail(SMASHX_E_ARG, "smashx_ann_host_gradient: null argument");
+    sx_annh_gradient(N, weights, (size_t)n, x, (size_t)nd, 1, loss_grad, weights_b);
+    return 0;
+}
+int smashx_ann_host_activation(int kind, long n, const double* x, double* y, double* dy) {
+    if (kind < SMASHX_ANN_RELU || kind > SMASHX_ANN_TANH) return fail(SMASHX_E_ARG, "smashx_ann_host_activation: SMASHX_ANN_RELU .. SMASHX_ANN_TANH expected");
+    if (n < 0 || (n > 0 && (!x || !y))) return fail(SMASHX_E_ARG, "smashx_ann_host_activation: null argument");
+    const SxAnnNet N{};
+    for (long i = 0; i < n; ++i) {
+        y[i] = sx_ann_value(N, kind, 0, x[i]);
+        if (dy) dy[i] = sx_ann_slope(N, kind, 0, x[i]);
+    }
+    return 0;
+}
+int smashx_ann_host_exp(long n, const double* x, double* y) {
+    if (n < 0 || (n > 0 && (!x || !y))) return fail(SMASHX_E_ARG, "smashx_ann_host_exp: null argument");
+    for (long i = 0; i < n; ++i) y[i] = sx_ann_exp(x[i]);
     return 0;
 }
 

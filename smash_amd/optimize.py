@@ -580,3 +580,135 @@ def optimize_hyper_lbfgsb(setup, mesh, input_data, parameters, states, output, v
     finally:
         input_data.descriptor = desc0
     return hist
+
+
+# ---- regionalisation by a neural network: Model.ann_optimize (smash/core/simulation/_ann_optimize.py, net.py:353-415) ------------------
+def ann_auto_graph(ntrain, nd, control_vector, bounds, optimizer="adam", learning_rate=0.003, random_state=None):
+    """_set_graph's network for net = None (_ann_optimize.py:140-175): dense(round(sqrt(ntrain nd) 2/3)) relu, dense(half of it) relu,
+    dense(ncv) sigmoid, scale(bounds), glorot_uniform kernels, compiled with the optimizer"""
+    from .net import Net
+    net = Net()
+    n_neurons = round(np.sqrt(ntrain * nd) * 2 / 3)
+    net.add(layer="dense", options={"input_shape": (nd,), "neurons": n_neurons, "kernel_initializer": "glorot_uniform"})
+    net.add(layer="activation", options={"name": "relu"})
+    net.add(layer="dense", options={"neurons": round(n_neurons / 2), "kernel_initializer": "glorot_uniform"})
+    net.add(layer="activation", options={"name": "relu"})
+    net.add(layer="dense", options={"neurons": len(control_vector), "kernel_initializer": "glorot_uniform"})
+    net.add(layer="activation", options={"name": "sigmoid"})
+    net.add(layer="scale", options={"bounds": bounds})
+    net.compile(optimizer=optimizer, random_state=random_state, options={"learning_rate": learning_rate})
+    return net
+
+
+def ann_optimize(setup, mesh, input_data, parameters, states, output, control_vector, bounds, net=None, optimizer="adam",
+                 learning_rate=0.003, epochs=400, early_stopping=False, random_state=None, verbose=False, device_map=True, evaluate=None):
+    """Mirror of _ann_optimize + Net._fit_d2p: a network maps the descriptors of a cell to the control fields (control_vector: names of
+    parameters / states, bounds (ncv, 2)); its weights are trained for `epochs` epochs on the cost of one adjoint run per epoch, by the
+    net's optimizer.  The descriptors are normalised in fp32 by their whole-grid minimum and maximum for the training and handed back
+    exactly as they were.  net = None builds the reference's graph (ann_auto_graph).  early_stopping keeps the weights of the epoch
+    with the lowest cost.  In place like the reference: the control fields come back as the network's outputs -- of the last epoch's
+    forward pass at the active cells, of the final weights elsewhere --, output holds the last epoch's run, net.history["loss_train"]
+    the cost per epoch.  Returns the net.
+
+    device_map = True: an epoch is ann_upload -> adjoint sweep -> ann_gradient on the device (include/smashx_ann.h); only the weights and
+    their gradient cross PCIe.  False: the host composition -- the host network (smashx_ann_host_*), forward_b, planes over PCIe --,
+    which computes the same bits.  A regulariser (setup.optimize.jreg_fun) is refused on the device path (SMASHX_E_UNSUPPORTED); the
+    host composition runs it against the fields as they were before the training, like the reference.  evaluate(planes) -> (cost, gradient planes), both dicts name -> (nrow, ncol) plane over the control
+    vector, replaces the sweep of the host composition (the loop can then run without a GPU).
+
+    The rows of the training set and the weight-gradient sums follow the active cells in column-major order (csrc/sx_ann.h); the
+    reference takes them in row-major order, which is the same mathematics in another order of summation."""
+    from .net import Net
+    from .solver import forward_b
+    control_vector = [str(k) for k in control_vector]
+    bounds = np.asarray(bounds, np.float64).reshape(len(control_vector), 2)
+    o = setup.optimize
+    for name, (lo, hi) in zip(control_vector, bounds):          # _ann_optimize.py:43-59
+        if name in PARAM_NAMES:
+            i = PARAM_NAMES.index(name)
+            o.optim_parameters[i], o.lb_parameters[i], o.ub_parameters[i] = 1, lo, hi
+        elif name in STATE_NAMES:
+            i = STATE_NAMES.index(name)
+            o.optim_states[i], o.lb_states[i], o.ub_states[i] = 1, lo, hi
+        else:
+            raise ValueError(f"control vector: {name!r} is neither a parameter nor a state")
+
+    desc0 = input_data.descriptor
+    desc = np.asfortranarray(desc0, dtype=np.float32).copy(order="F")
+    nd = desc.shape[2]
+    for i in range(nd):                                         # _normalize_descriptor (_optimize.py:801-810), fp32
+        lo, hi = np.amin(desc[..., i]), np.amax(desc[..., i])
+        desc[..., i] = (desc[..., i] - lo) / (hi - lo)
+    active = np.asarray(mesh.active_cell) == 1
+    cc, rr = np.nonzero(active.T)                               # the active cells in column-major order
+    ci, ri = np.nonzero(~active.T)
+    x_train, x_inactive = np.ascontiguousarray(desc[rr, cc]), np.ascontiguousarray(desc[ri, ci])
+
+    if net is None:
+        net = ann_auto_graph(len(x_train), nd, control_vector, bounds, optimizer, learning_rate, random_state)
+    elif not isinstance(net, Net):
+        raise ValueError(f"Unknown network {net}")
+    elif not net.layers:
+        raise ValueError("The graph has not been set yet")
+    else:
+        ips, ios = net.layers[0].input_shape, net.layers[-1].output_shape()
+        if ips[0] != nd:
+            raise ValueError(f"Inconsistent value between the number of input layer ({ips}) and the number of descriptors ({nd}): {ips[0]} != {nd}")
+        if ios[0] != len(control_vector):
+            raise ValueError(f"Inconsistent value between the number of output layer ({ios}) and the number of control vectors "
+                             f"({len(control_vector)}): {ios[0]} != {len(control_vector)}")
+    if not net._compiled:
+        raise ValueError("The network has not been compiled yet")
+
+    def plane_of(name):
+        return getattr(parameters if name in PARAM_NAMES else states, name)
+
+    def set_planes(y, r, c):
+        for i, name in enumerate(control_vector):
+            plane_of(name)[r, c] = y[:, i]
+
+    injected = evaluate is not None
+    input_data.descriptor = desc
+    try:
+        if not injected and device_map:
+            sol = _solver_for(setup, mesh, input_data)
+            sol.set_ann_descriptors(desc)
+            sol.set_ann_net(net, control_vector)
+            sol.upload(parameters, states, parameters, states)
+        elif not injected:
+            par_b, sta_b = parameters.copy(), states.copy()
+            par_bgd, sta_bgd = parameters.copy(), states.copy()        # the background of every epoch: the fields before the training
+        loss_opt, best = 0, None
+        for epo in range(int(epochs)):
+            w = net.weights()
+            if not injected and device_map:
+                sol.ann_upload(w)
+                sol.sweep(True, 1.0)
+                loss = sol.cost_and_qsim(output)
+                grad = sol.ann_gradient()
+            else:
+                set_planes(net._forward_pass(x_train), rr, cc)
+                if injected:
+                    loss, gp = evaluate({k: plane_of(k) for k in control_vector})
+                else:
+                    loss = forward_b(setup, mesh, input_data, parameters, par_b, par_bgd, par_b, states, sta_b, sta_bgd, sta_b,
+                                     output, None, np.float32(0), np.float32(1))
+                    gp = {k: getattr(par_b if k in PARAM_NAMES else sta_b, k) for k in control_vector}
+                loss_grad = np.stack([np.asarray(gp[k], np.float32)[rr, cc] for k in control_vector], axis=1)
+                grad = net.gradient(x_train, loss_grad)
+            loss = float(np.float32(loss))
+            if early_stopping and (loss_opt > loss or epo == 0):
+                loss_opt, best = loss, w
+            net.update(grad)
+            if verbose:
+                print(f"    At epoch {epo + 1:3d}    J = {loss:10.6f}    |proj g| = {float(np.max(np.abs(grad))) if grad.size else 0.0:10.6f}")
+            net.history["loss_train"].append(loss)
+        if early_stopping and best is not None:
+            net.set_weights(best)
+        if not injected and device_map and int(epochs) > 0:
+            sol.ann_fields(parameters, states)
+        if len(x_inactive):
+            set_planes(net._predict(x_inactive), ri, ci)        # the predicted map at the inactive cells, so that the planes come back whole
+    finally:
+        input_data.descriptor = desc0
+    return net

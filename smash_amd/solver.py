@@ -520,6 +520,84 @@ class Solver:
         return {"nd": info[0], "nhyper": info[1], "chains": info[2], "span": info[3], "map_ms": float(ms[0]), "gradient_ms": float(ms[1])}
 
 
+    # -- the ANN regionalisation on the device (include/smashx_ann.h) ------------------------------------
+    def set_ann_descriptors(self, descriptor):
+        """The NORMALISED descriptors (nrow, ncol, nd), float32 Fortran order, into HBM (smashx_ann_set_descriptors); handing over what
+        the plan already holds moves nothing."""
+        nd, desc = check_ann_descriptors(self.nrow, self.ncol, descriptor)
+        _lib.check(_lib.lib().smashx_ann_set_descriptors(self._h, nd, _ptr(desc)))
+
+    def set_ann_net(self, net, control_vector):
+        """The graph of a smash_amd.Net and the fields its outputs go to: control_vector names parameters / states, one per output
+        (smashx_ann_set_net).  Behind set_ann_descriptors, whose nd is the net's input width."""
+        nd, kind, width, ncv, lower, upper = net.graph()
+        field = check_ann_control_vector(control_vector, ncv)
+        if lower is not None and lower.size != ncv:
+            raise _lib.SmashxError(_lib.E_ARG, f"ann net: the scale layer has {lower.size} bounds, the network {ncv} outputs")
+        _lib.check(_lib.lib().smashx_ann_set_net(self._h, len(kind), _ptr(kind), _ptr(width), ncv, _ptr(field), _ptr(lower), _ptr(upper)))
+        self._ann_nw = int(sum((l.input_shape[0] + 1) * l.neurons for l in net._dense()))
+
+    def ann_upload(self, weights):
+        """The network at every active cell into the control fields, behind an upload() of the background fields and in front of
+        sweep(): weights packed float64 (Net.weights())."""
+        _lib.check(_lib.lib().smashx_ann_upload(self._h, _ptr(check_ann_weights(getattr(self, "_ann_nw", None), weights))))
+
+    def ann_gradient(self, weights_b=None):
+        """After an adjoint sweep: the gradient w.r.t. the packed weights, float64 (the array given -- overwritten -- or a new one)."""
+        nw = getattr(self, "_ann_nw", None)
+        if weights_b is None and nw is not None:
+            weights_b = np.zeros(nw, np.float64)
+        wb = check_ann_weights(nw, weights_b, writeable=True)
+        _lib.check(_lib.lib().smashx_ann_gradient(self._h, _ptr(wb)))
+        return wb
+
+    def ann_fields(self, parameters=None, states=None):
+        """The mapped control fields of the last ann_upload into the planes of parameters / states (either may be None): their active
+        cells are written, everything else stays."""
+        P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
+        S, k2 = _pack(states, STATE_NAMES, _lib.States)
+        for keep in (k1, k2):
+            for a in keep:
+                if a.shape != (self.nrow, self.ncol) or not a.flags.writeable:
+                    raise _lib.SmashxError(_lib.E_ARG, f"ann_fields: every plane must be a writeable ({self.nrow}, {self.ncol}) array")
+        _lib.check(_lib.lib().smashx_ann_fields(self._h, C.byref(P), C.byref(S)))
+
+    def ann_info(self):
+        """{nd, nweights, span, lds_bytes, map_ms, gradient_ms} of the last ann_upload / ann_gradient on this plan (smashx_ann_info)."""
+        info, ms = (C.c_int * 4)(), (C.c_float * 2)()
+        _lib.check(_lib.lib().smashx_ann_info(self._h, info, ms))
+        return {"nd": info[0], "nweights": info[1], "span": info[2], "lds_bytes": info[3], "map_ms": float(ms[0]), "gradient_ms": float(ms[1])}
+
+
+def check_ann_descriptors(nrow, ncol, descriptor):
+    """Argument checks of set_ann_descriptors, before anything reaches the C call: (nd, descriptor)"""
+    d = descriptor
+    if (not isinstance(d, np.ndarray) or d.ndim != 3 or d.shape[:2] != (nrow, ncol) or d.shape[2] < 1 or d.dtype != np.float32
+            or not d.flags.f_contiguous):
+        raise _lib.SmashxError(_lib.E_ARG, f"ann descriptors: a Fortran-ordered float32 array of shape ({nrow}, {ncol}, nd >= 1) expected")
+    return d.shape[2], d
+
+
+def check_ann_control_vector(control_vector, ncv):
+    """names of parameters / states, one per output of the network -> their field numbers (0 .. 15 parameters, 16 .. 23 states), int32"""
+    names = [str(k) for k in control_vector]
+    both = list(PARAM_NAMES) + list(STATE_NAMES)
+    if len(names) != ncv or len(set(names)) != len(names) or any(k not in both for k in names):
+        raise _lib.SmashxError(_lib.E_ARG, f"ann control vector: {ncv} distinct names of parameters / states expected, got {names}")
+    return np.array([both.index(k) for k in names], np.int32)
+
+
+def check_ann_weights(nweights, weights, writeable=False):
+    """Argument checks of ann_upload / ann_gradient: a contiguous float64 vector of the net's packed length"""
+    if nweights is None:
+        raise _lib.SmashxError(_lib.E_STATE, "ann weights: no net set (set_ann_net)")
+    w = weights
+    if (not isinstance(w, np.ndarray) or w.shape != (nweights,) or w.dtype != np.float64 or not w.flags.c_contiguous
+            or (writeable and not w.flags.writeable)):
+        raise _lib.SmashxError(_lib.E_ARG, f"ann weights: a {'writeable ' if writeable else ''}contiguous float64 vector of length {nweights} expected")
+    return w
+
+
 def check_hyper_descriptors(nrow, ncol, mapping, descriptor):
     """Argument checks of set_hyper_descriptors, before anything reaches the C call (an array of another shape, type or order would be
     read out of bounds or scrambled).  Returns (mapping code, nd, descriptor) ready for the call -- descriptor None (drop) gives
