@@ -437,6 +437,8 @@ int smashx_lbfgsb_destroy(smashx_lbfgsb* opt);
 #include "smashx_hyper.h"
 /* ---- the ANN regionalisation on the device (ann_optimize) and the same network on the host: declared in smashx_ann.h, likewise ---------- */
 #include "smashx_ann.h"
+/* ---- the uniform calibration (optimize_sbs) and the cost of a batch of uniform candidates: declared in smashx_sbs.h, likewise ----------- */
+#include "smashx_sbs.h"
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """ctypes view of include/smashx.h, declared once: the header's constants, one class per struct (STRUCTS), one prototype per function
-(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h, PRCP_PROTOTYPES for include/smashx_prcp.h, SIGNATURE_PROTOTYPES for include/smashx_signature.h HYPER_DEVICE_PROTOTYPES for include/smashx_hyper.h and ANN_PROTOTYPES for include/smashx_ann.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
+(PROTOTYPES; SETUP_PROTOTYPES for include/smashx_setup.h, FORCING_PROTOTYPES for include/smashx_forcing.h, PRCP_PROTOTYPES for include/smashx_prcp.h, SIGNATURE_PROTOTYPES for include/smashx_signature.h HYPER_DEVICE_PROTOTYPES for include/smashx_hyper.h, ANN_PROTOTYPES for include/smashx_ann.h and SBS_PROTOTYPES for include/smashx_sbs.h, which smashx.h includes).  tests/test_abi_header_cpu.py compares all three with the header's text; adding an entry point is one line in
 PROTOTYPES.  Loading fails loudly when libsmashx.so is missing: there is no Python / CPU implementation of the solver behind this
 module."""
 from __future__ import annotations
@@ -210,6 +210,24 @@ ANN_PROTOTYPES = {
     "smashx_ann_host_exp": (_int, [_long, ptr, ptr]),
 }
 ANN_SYMBOLS = list(ANN_PROTOTYPES)
+# ---- every function of include/smashx_sbs.h (the optimiser of optimize_sbs in ask / tell form and the cost of a batch of uniform
+# candidates on the catchment-resident kernel, which smashx.h includes as well), the same way; tests/test_sbs_cpu.py reads that header
+# and compares
+SBS_PROTOTYPES = {
+    "smashx_sbs_create": (_int, [_int, ptr, ptr, ptr, _float, _int, _out]),
+    "smashx_sbs_ask": (_int, [ptr, ptr, ptr]),
+    "smashx_sbs_tell": (_int, [ptr, ptr]),
+    "smashx_sbs_x": (_int, [ptr, ptr]),
+    "smashx_sbs_gx": (_float, [ptr]),
+    "smashx_sbs_ddx": (_float, [ptr]),
+    "smashx_sbs_iter": (_int, [ptr]),
+    "smashx_sbs_nfg": (_int, [ptr]),
+    "smashx_sbs_message": (_str, [ptr]),
+    "smashx_sbs_destroy": (_int, [ptr]),
+    "smashx_uniform_costs": (_int, [ptr, _par, _sta, _int, ptr, ptr, _int, ptr]),
+    "smashx_uniform_costs_info": (_int, [ptr, ptr, ptr]),
+}
+SBS_SYMBOLS = list(SBS_PROTOTYPES)
 
 
 class SmashxError(RuntimeError):
@@ -230,7 +248,7 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: build the HIP library first (__graft_entry__.build()); "
                               "smash_amd has no CPU fallback")
         L = C.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()) + list(SIGNATURE_PROTOTYPES.items()) + list(HYPER_DEVICE_PROTOTYPES.items()) + list(ANN_PROTOTYPES.items()):
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(SETUP_PROTOTYPES.items()) + list(FORCING_PROTOTYPES.items()) + list(PRCP_PROTOTYPES.items()) + list(SIGNATURE_PROTOTYPES.items()) + list(HYPER_DEVICE_PROTOTYPES.items()) + list(ANN_PROTOTYPES.items()) + list(SBS_PROTOTYPES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         # the structs above mirror include/smashx.h by hand: refuse a library built from another layout (a stale .so would have

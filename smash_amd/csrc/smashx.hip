@@ -20,6 +20,7 @@
 #include "sx_jreg.h"
 #include "sx_kernels.h"
 #include "sx_ensemble.h"
+#include "sx_resident.h"
 #include "sx_fields.h"
 #include "sx_interception.h"
 #include "sx_meanforcing.h"
@@ -494,6 +495,14 @@ struct smashx_plan {
         hipEvent_t ev_a = nullptr, ev_b = nullptr;
         int info[4] = {0, 0, 0, 0};      // batch size, time chunk, batches, chunks per batch of the last call
         float device_ms = 0.f;
+        // catchment-resident path (smashx_uniform_costs, sx_resident.h): host copies of the forest and the per-thread tables built from them
+        std::vector<int> h_up, h_upn, h_order, h_level;
+        int res_state = 0;               // 0 = not built, 1 = ready, 2 = refused (res_refusal says why)
+        std::string res_refusal;
+        int *r_cell = nullptr, *r_level = nullptr, *r_upline = nullptr, *r_upn = nullptr, *r_ownline = nullptr, *r_gfirst = nullptr, *r_gnext = nullptr;
+        int res_block = 0; size_t res_lds = 0, res_static = 0;
+        int res_info[4] = {0, 0, 0, 0};  // cells, levels, workgroup size, LDS bytes of the last call
+        float res_ms = 0.f;
     } ens;
 
     template <class T> int dmalloc(T** p, size_t count) {
@@ -2698,6 +2707,7 @@ int ens_tables(smashx_plan* p) {
     if ((rc = p->dmalloc(&E.plane, (size_t)p->n2))) return rc;
     HIPCHK(hipEventCreate(&E.ev_a)); HIPCHK(hipEventCreate(&E.ev_b));
     E.nlevels = nlev; E.level_begin = begin; E.tables = true;
+    E.h_up = up; E.h_upn = upn; E.h_order = order; E.h_level = level;
     return 0;
 }
 
@@ -2847,6 +2857,185 @@ int smashx_multiple_run_info(const smashx_plan* p, int info[4], float* device_ms
     if (!p) return fail(SMASHX_E_ARG, "null plan");
     if (info) for (int i = 0; i < 4; ++i) info[i] = p->ens.info[i];
     if (device_ms) *device_ms = p->ens.device_ms;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// catchment-resident path: smashx_uniform_costs (include/smashx_sbs.h).  Kernel and hand-off: sx_resident.h.  One workgroup per
+// sample, so a batch is one launch of SP workgroups followed by the ensemble's two cost kernels on qg [g][t][SP]; the columns past
+// the last sample hold whatever the buffer held (nothing of them is copied out).
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+// the per-thread tables of sx_k_res_fwd from the forest of ens_tables; a catchment beyond the kernel's limits is refused once and for all
+int res_tables(smashx_plan* p) {
+    auto& X = p->ens;
+    if (X.res_state) return 0;
+    const int n = p->n, ng = p->ng;
+    if (n > SX_RES_MAXCELLS) {
+        X.res_state = 2;
+        X.res_refusal = std::to_string(n) + " active cells, the resident kernel holds one cell per thread and at most " + std::to_string(SX_RES_MAXCELLS);
+        return 0;
+    }
+    std::vector<int> pos(n), parent(n, -1), own(n, -1), cell(n), level(n), upn(n), upline((size_t)n * 8, 0), gfirst(n, -1), gnext(std::max(ng, 1), -1);
+    for (int i = 0; i < n; ++i) pos[X.h_order[i]] = i;
+    for (int k = 0; k < n; ++k)
+        for (int c = 0; c < X.h_upn[k]; ++c) parent[X.h_up[(size_t)k * 8 + c]] = k;
+    size_t floats = 0;
+    for (int i = 0; i < n; ++i) {          // lines in thread order: neighbours in a level are neighbours in LDS
+        const int k = X.h_order[i];
+        cell[i] = k; level[i] = X.h_level[k]; upn[i] = X.h_upn[k];
+        if (parent[k] < 0) continue;
+        const int D = X.h_level[parent[k]] - X.h_level[k];     // >= 1
+        int lg = 1;
+        while ((1 << lg) < D + 1) ++lg;                          // D + 1 slots, rounded up to a power of two (sx_resident.h)
+        if (floats + ((size_t)1 << lg) > ((size_t)1 << 26)) { floats = (size_t)1 << 26; break; }
+        own[i] = (int)(floats << 5) | lg;
+        floats += (size_t)1 << lg;
+    }
+    // what a workgroup may claim: the device's limit less what the kernel holds statically (the exact-libm build's tables)
+    int lim = 0, dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    HIPCHK(hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    hipFuncAttributes fa{};
+    HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&sx_k_res_fwd<1>)));
+    X.res_static = fa.sharedSizeBytes;
+    if (floats * 4 + X.res_static > (size_t)lim) {
+        X.res_state = 2;
+        X.res_refusal = "the delay lines of the catchment need " + (floats >= ((size_t)1 << 26) ? std::string("more than 268435456") : std::to_string(floats * 4 + X.res_static)) +
+                        " B of LDS, a workgroup may claim " + std::to_string(lim);
+        return 0;
+    }
+    for (int i = 0; i < n; ++i) {
+        const int k = cell[i];
+        for (int c = 0; c < upn[i]; ++c) upline[(size_t)i * 8 + c] = own[pos[X.h_up[(size_t)k * 8 + c]]];
+    }
+    for (int g = ng - 1; g >= 0; --g) {      // gauges of a cell chained in gauge order
+        const int k = p->sch.gauge_k[g];
+        if (k < 0 || k >= n) continue;
+        gnext[g] = gfirst[pos[k]]; gfirst[pos[k]] = g;
+    }
+    int rc;
+    if ((rc = p->upload_vec(&X.r_cell, cell)) || (rc = p->upload_vec(&X.r_level, level)) || (rc = p->upload_vec(&X.r_upline, upline)) ||
+        (rc = p->upload_vec(&X.r_upn, upn)) || (rc = p->upload_vec(&X.r_ownline, own)) || (rc = p->upload_vec(&X.r_gfirst, gfirst)) ||
+        (rc = p->upload_vec(&X.r_gnext, gnext))) return rc;
+    X.res_block = std::max(64, (n + 63) / 64 * 64);
+    X.res_lds = floats * 4;
+    X.res_state = 1;
+    return 0;
+}
+
+extern "C++" {
+template <int ST>
+int res_launch(smashx_plan* p, const SxEnsArrays& E, const SxResTables& R, int SP, hipStream_t sV) {
+    auto& X = p->ens;
+    if (X.res_lds > 48 * 1024)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sx_k_res_fwd<ST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X.res_lds));
+    hipLaunchKernelGGL((sx_k_res_fwd<ST>), dim3(SP), dim3(X.res_block), X.res_lds, sV, p->A, E, R, p->nt);
+    return 0;
+}
+}  // extern "C++"
+}  // namespace
+
+int smashx_uniform_costs(smashx_plan* p, const smashx_parameters* params, const smashx_states* states, int nfields,
+                         const int* ind, const float* sample, int nsamples, float* res_cost) {
+    if (!p || !params || !states || !res_cost) return fail(SMASHX_E_ARG, "smashx_uniform_costs: null argument (plan, parameters, states, res_cost)");
+    if (nsamples < 1) return fail(SMASHX_E_ARG, "smashx_uniform_costs: nsamples < 1");
+    if (nfields < 0 || nfields > SMASHX_GNP + SMASHX_GNS || (nfields > 0 && (!ind || !sample))) return fail(SMASHX_E_ARG, "smashx_uniform_costs: bad nfields / null index list or sample");
+    const int st = p->st;
+    int smap[SX_ENS_NP + SX_ENS_NS];
+    for (int& v : smap) v = -1;
+    for (int j = 0; j < nfields; ++j) {
+        const int f = ind[j];
+        if (f < 1 || f > SMASHX_GNP + SMASHX_GNS) return fail(SMASHX_E_ARG, "smashx_uniform_costs: ind_parameters_states[" + std::to_string(j) + "] = " + std::to_string(f) + " is outside 1..24");
+        const int slot = sx_field_slot(st, f - 1);
+        if (slot < 0) return fail(SMASHX_E_ARG, "smashx_uniform_costs: field " + std::to_string(f) + " is not used by the structure");
+        if (smap[slot] >= 0) return fail(SMASHX_E_ARG, "smashx_uniform_costs: field " + std::to_string(f) + " is listed twice");
+        smap[slot] = j;
+    }
+    if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: denormalize_forward is not supported (the reference's optimize_sbs never sets it)");
+    if (p->opt.wjreg != 0.f && p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: wjreg with a regulariser (jreg_fun) is not supported");
+    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: a tiled plan (tile / owner_mask) is not supported");
+    if (wants_signature(p->opt)) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: signature-based jobs_fun are not built into the ensemble cost");
+    if (p->n > SX_RES_MAXCELLS) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: " + std::to_string(p->n) + " active cells, the resident kernel holds one cell per thread and at most " + std::to_string(SX_RES_MAXCELLS));
+    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
+    int rc = set_device(p); if (rc) return rc;
+    if ((rc = ens_tables(p))) return rc;
+    if ((rc = res_tables(p))) return rc;
+    auto& X = p->ens;
+    if (X.res_state == 2) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: " + X.res_refusal);
+    hipStream_t sV = p->stream;
+    if ((rc = close_forcing(p))) return rc;
+    const int n = p->n, nt = p->nt, ng = p->ng;
+
+    // base fields in cell order; a sampled field needs no base
+    const dim3 b256(256), gk((n + 255) / 256);
+    for (int slot = 0; slot < SX_ENS_NP + SX_ENS_NS; ++slot) {
+        const bool isp = !sx_slot_is_state(slot);
+        const int f = sx_slot_field(st, slot);
+        if (f < 0 || smap[slot] >= 0) continue;
+        const float* h = host_plane(params, states, f);
+        if (!h) return fail(SMASHX_E_ARG, std::string("smashx_uniform_costs: a ") + (isp ? "parameter" : "state") + " field the structure uses is NULL and not sampled");
+        HIPCHK(hipMemcpyAsync(X.plane, h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
+        hipLaunchKernelGGL(k_gather, gk, b256, 0, sV, X.base + (size_t)slot * p->npad, X.plane, p->d_cell_flat, n);
+    }
+
+    const int SP = std::min((nsamples + 63) / 64 * 64, 16384);       // samples per batch: one launch of SP workgroups
+    const int nbatch = (nsamples + SP - 1) / SP;
+    const size_t sSP = (size_t)SP;
+    if ((rc = ens_grow(p, &X.sample, &X.cap_sample, (size_t)std::max(nfields, 1) * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.qg, &X.cap_qg, (size_t)std::max(ng, 1) * nt * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.gj, &X.cap_gj, (size_t)2 * std::max(ng, 1) * sSP))) return rc;
+    if ((rc = ens_grow(p, &X.cost, &X.cap_cost, sSP))) return rc;
+
+    SxEnsArrays E{};
+    E.n = n; E.npad = p->npad; E.SP = SP; E.Tc = nt;
+    E.base = X.base; E.sample = X.sample;
+    for (int i = 0; i < SX_ENS_NP + SX_ENS_NS; ++i) E.smap[i] = smap[i];
+    E.up = X.d_up; E.upn = X.d_upn; E.order = X.d_order;
+    E.qg = X.qg; E.gauge_k = X.d_gauge_k; E.gj = X.gj; E.med = X.gj + (size_t)std::max(ng, 1) * sSP; E.cost = X.cost;
+    SxResTables R{};
+    R.nlevels = X.nlevels; R.cell = X.r_cell; R.level = X.r_level; R.upline = X.r_upline; R.upn = X.r_upn; R.ownline = X.r_ownline;
+    R.gfirst = X.r_gfirst; R.gnext = X.r_gnext;
+    const SxCostArgs C = cost_args(p, 0.f);
+    const dim3 b64(64), gS(SP / 64);
+    std::vector<float> hs((size_t)std::max(nfields, 1) * sSP), hc(sSP), out(nsamples);
+    X.res_ms = 0.f;
+    for (int bi = 0; bi < nbatch; ++bi) {
+        const int s0 = bi * SP, cnt = std::min(SP, nsamples - s0);
+        for (int j = 0; j < nfields; ++j)
+            for (int c = 0; c < SP; ++c) hs[(size_t)j * sSP + c] = sample[(size_t)j + (size_t)nfields * (s0 + std::min(c, cnt - 1))];
+        HIPCHK(hipEventRecord(X.ev_a, sV));
+        if (nfields > 0) HIPCHK(hipMemcpyAsync(X.sample, hs.data(), (size_t)nfields * sSP * 4, hipMemcpyHostToDevice, sV));
+        if (ng > 0) {       // without a gauge the cost is 0 and nothing has to run
+            switch (st) {
+                case 1: rc = res_launch<1>(p, E, R, cnt, sV); break;
+                case 2: rc = res_launch<2>(p, E, R, cnt, sV); break;
+                case 3: rc = res_launch<3>(p, E, R, cnt, sV); break;
+                case 4: rc = res_launch<4>(p, E, R, cnt, sV); break;
+                default: rc = res_launch<5>(p, E, R, cnt, sV); break;
+            }
+            if (rc) return rc;
+            hipLaunchKernelGGL(sx_k_ens_cost_gauge, dim3(SP / 64, ng), b64, 0, sV, C, E);
+            hipLaunchKernelGGL(sx_k_ens_cost_final, gS, b64, 0, sV, C, E);
+            HIPCHK(hipMemcpyAsync(hc.data(), X.cost, (size_t)cnt * 4, hipMemcpyDeviceToHost, sV));
+        }
+        HIPCHK(hipEventRecord(X.ev_b, sV));
+        HIPCHK(hipStreamSynchronize(sV));
+        HIPCHK(hipGetLastError());
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, X.ev_a, X.ev_b) == hipSuccess) X.res_ms += ms;
+        // cost = jobs + wjreg * jreg with jreg = 0 (mwd_cost.f90:300), as smashx_download forms it
+        for (int c = 0; c < cnt; ++c) out[s0 + c] = (ng > 0 ? hc[c] : 0.f) + p->opt.wjreg * 0.f;
+    }
+    for (int i = 0; i < nsamples; ++i) res_cost[i] = out[i];      // only a complete call writes res_cost
+    X.res_info[0] = n; X.res_info[1] = X.nlevels; X.res_info[2] = X.res_block; X.res_info[3] = (int)(X.res_lds + X.res_static);
+    return 0;
+}
+
+int smashx_uniform_costs_info(const smashx_plan* p, int info[4], float* device_ms) {
+    if (!p) return fail(SMASHX_E_ARG, "null plan");
+    if (info) for (int i = 0; i < 4; ++i) info[i] = p->ens.res_info[i];
+    if (device_ms) *device_ms = p->ens.res_ms;
     return 0;
 }
 

@@ -423,6 +423,137 @@ def optimize_lbfgsb(setup, mesh, input_data, parameters, states, output, verbose
     return hist
 
 
+# ---- uniform calibration: mw_optimize::optimize_sbs (mw_optimize.f90:53-294) -----------------------------------------------------------
+# "auto" takes the catchment-resident kernel for a batch of at least this many candidates, when smashx_uniform_costs accepts the plan
+# and the options.  Measured (profiles/uniform_costs.json): a resident call costs one launch whatever the batch -- 2.6 ms
+# on Cance, 17.5 ms on 32 x 32 x 8760 -- and a forward of the loop 1.45 ms / 8.5 ms, so the loop wins for 1 candidate (the line-search
+# point of an iteration), 2 are a tie (Cance to the kernel, the synthetic case to the loop, both by less than 10 %) and the kernel wins from 3.
+SBS_AUTO_MIN_CANDIDATES = 3
+
+
+def optimize_sbs(setup, mesh, input_data, parameters, states, output, verbose=False, candidates="auto"):
+    """The mirror of mw_optimize::optimize_sbs, the reference's default calibration (mapping="uniform", algorithm="sbs"): in place,
+    parameters / states come back with the calibrated value of every optimised field on the active cells (inactive cells keep
+    theirs), output holds the final run.  The control vector and its bounds are the fields flagged in setup.optimize.optim_parameters
+    / optim_states with lb_* / ub_* in stacked order (bounds_initialise_sbs), the start point is read at the first active cell in
+    column-major order (var_to_control_sbs), setup.optimize.maxiter bounds the iterations (default 100).  The optimiser is the
+    library's (smashx_sbs_*: the reference's loop restated in fp32, ask / tell); the initial and the final evaluation are forward().
+
+    candidates: how the batch of candidates of a stage is evaluated -- "resident": smashx_uniform_costs, one workgroup per candidate;
+    "ensemble": smashx_multiple_run; "loop": one forward per candidate; "auto": resident when it accepts the plan and the options and
+    the batch has SBS_AUTO_MIN_CANDIDATES candidates, else the loop.  The three give the same costs bit for bit, hence the same
+    trajectory.  Returns a dict: per completed iterate k (the reference's iter / n) the cost, the point, nfg and ddx; the message."""
+    import ctypes as C
+    from . import _lib
+    from .solver import FIELD_NAMES
+    if candidates not in ("auto", "resident", "ensemble", "loop"):
+        raise ValueError(f"candidates must be 'auto', 'resident', 'ensemble' or 'loop', not {candidates!r}")
+    o = setup.optimize
+    maxiter = int(getattr(o, "maxiter", 100))
+    optim = list(np.asarray(o.optim_parameters).reshape(-1)) + list(np.asarray(o.optim_states).reshape(-1))
+    lb = list(np.asarray(o.lb_parameters, np.float32).reshape(-1)) + list(np.asarray(o.lb_states, np.float32).reshape(-1))
+    ub = list(np.asarray(o.ub_parameters, np.float32).reshape(-1)) + list(np.asarray(o.ub_states, np.float32).reshape(-1))
+    fields = [i for i in range(len(FIELD_NAMES)) if optim[i] > 0]
+    n = len(fields)
+    if n == 0:
+        raise ValueError("nothing to optimise: optim_parameters / optim_states are all zero")
+    names = [FIELD_NAMES[i] for i in fields]
+    ind = np.array([i + 1 for i in fields], np.int32)
+    lower = np.array([lb[i] for i in fields], np.float32)
+    upper = np.array([ub[i] for i in fields], np.float32)
+    act = np.asarray(mesh.active_cell) == 1
+    if not act.any():
+        raise ValueError("the mesh has no active cell")
+    first = int(np.argmax(act.reshape(-1, order="F")))         # maxloc(mesh%active_cell): the first active cell, column-major
+    r0, c0 = first % act.shape[0], first // act.shape[0]
+
+    def holder(k):
+        return parameters if k in PARAM_NAMES else states
+
+    def plane(obj, k):
+        a = getattr(obj, k)
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.f_contiguous):
+            a = np.asfortranarray(a, dtype=np.float32)
+            setattr(obj, k, a)
+        return a
+
+    def control_to_var(par, sta, x):           # where (mask) matrix(:, :, i) = x(j)
+        for k, v in zip(names, x):
+            plane(par if k in PARAM_NAMES else sta, k)[act] = np.float32(v)
+
+    x0 = np.array([plane(holder(k), k)[r0, c0] for k in names], np.float32)
+    par_bgd, sta_bgd = parameters.copy(), states.copy()
+    forward(setup, mesh, input_data, parameters, par_bgd, states, sta_bgd, output, np.float32(0))
+    cost0 = np.float32(output.cost)
+    hist = {"cost": [float(cost0)], "x": [x0.copy()], "nfg": [1], "ddx": [0.64], "fields": names, "task": "", "route": candidates}
+    if verbose:
+        print(f"    At iterate    {0:3d}    nfg = {1:5d}    J ={float(cost0):10.6f}    ddx ={0.64:5.2f}")
+
+    sol = _solver_for(setup, mesh, input_data)
+    route = {"use": candidates}
+    trial_par, trial_sta = parameters.copy(), states.copy()
+
+    def costs_of(y):
+        m = y.shape[1]
+        use = route["use"]
+        if use == "auto":
+            use = "resident" if m >= SBS_AUTO_MIN_CANDIDATES else "loop"
+        if use == "resident":
+            try:
+                return sol.uniform_costs(parameters, states, y, ind)
+            except _lib.SmashxError as e:
+                if route["use"] != "auto" or e.code != _lib.E_UNSUPPORTED:
+                    raise
+                route["use"] = "loop"           # signature criteria, a regulariser, a catchment over the kernel's limits: the loop runs them all
+                hist["route"] = "auto -> loop: " + str(e)
+        elif use == "ensemble":
+            return sol.multiple_run(parameters, states, y, ind)
+        f = np.zeros(m, np.float32)
+        for c in range(m):
+            control_to_var(trial_par, trial_sta, y[:, c])
+            forward(setup, mesh, input_data, trial_par, par_bgd, trial_sta, sta_bgd, output, np.float32(0))
+            f[c] = np.float32(output.cost)
+        return f
+
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.smashx_sbs_create(n, lower.ctypes.data, upper.ctypes.data, x0.ctypes.data, C.c_float(float(cost0)), maxiter, C.byref(h)))
+    try:
+        ybuf = np.zeros((n, 2 * n), np.float32, order="F")
+        m = C.c_int(0)
+        x = x0.copy()
+        done = 0
+        while True:
+            _lib.check(L.smashx_sbs_ask(h, ybuf.ctypes.data, C.byref(m)))
+            if m.value == 0:
+                break
+            f = np.ascontiguousarray(costs_of(np.asfortranarray(ybuf[:, :m.value])), np.float32)
+            _lib.check(L.smashx_sbs_tell(h, f.ctypes.data))
+            it = L.smashx_sbs_iter(h)
+            if it != done:
+                done = it
+                _lib.check(L.smashx_sbs_x(h, x.ctypes.data))
+                control_to_var(parameters, states, x)           # the base of the next stage's candidates is the current point
+                control_to_var(trial_par, trial_sta, x)
+                if it % n == 0:
+                    gx, ddx, nfg = float(L.smashx_sbs_gx(h)), float(L.smashx_sbs_ddx(h)), int(L.smashx_sbs_nfg(h))
+                    hist["cost"].append(gx); hist["x"].append(x.copy()); hist["nfg"].append(nfg); hist["ddx"].append(ddx)
+                    if verbose:
+                        print(f"    At iterate    {it // n:3d}    nfg = {nfg:5d}    J ={gx:10.6f}    ddx ={ddx:5.2f}")
+        hist["task"] = L.smashx_sbs_message(h).decode()
+        hist["iter"], hist["nfg_total"] = int(L.smashx_sbs_iter(h)), int(L.smashx_sbs_nfg(h))
+        if hist["task"]:           # one of the reference's two stopping rules: the final evaluation at x
+            if verbose:
+                print("    " + hist["task"] + "\n")
+            _lib.check(L.smashx_sbs_x(h, x.ctypes.data))
+            control_to_var(parameters, states, x)
+            forward(setup, mesh, input_data, parameters, par_bgd, states, sta_bgd, output, np.float32(0))
+        hist["final_cost"], hist["final_x"] = float(np.float32(output.cost)), x.copy()
+    finally:
+        L.smashx_sbs_destroy(h)
+    return hist
+
+
 # ---- regionalisation: mw_optimize::optimize_hyper_lbfgsb (mw_optimize.f90:779-1177) ---------------------------------------------------
 def _logf(x):
     """logf of the C library, which the reference's compiled code calls (numpy's float32 log is another implementation)"""

@@ -447,6 +447,24 @@ class Solver:
         _lib.check(_lib.lib().smashx_multiple_run_info(self._h, info, C.byref(ms)))
         return {"batch": info[0], "chunk": info[1], "n_batches": info[2], "n_chunks": info[3], "device_ms": float(ms.value)}
 
+    def uniform_costs(self, parameters, states, sample, ind_parameters_states, *, res_cost=None):
+        """The cost of S spatially uniform candidates on the catchment-resident kernel (smashx_uniform_costs): the arguments and the
+        result of multiple_run without the discharge.  Returns res_cost (S,).  parameters / states are read only."""
+        sample, ind = check_multiple_run(self.structure, self.ng, self.nt, sample, ind_parameters_states, res_cost)
+        nf, S = sample.shape
+        if res_cost is None:
+            res_cost = np.zeros(S, np.float32)
+        P, k1 = _pack_const(parameters, PARAM_NAMES, _lib.Parameters)
+        St, k2 = _pack_const(states, STATE_NAMES, _lib.States)
+        _lib.check(_lib.lib().smashx_uniform_costs(self._h, C.byref(P), C.byref(St), nf, _ptr(ind), _ptr(sample), S, _ptr(res_cost)))
+        return res_cost
+
+    def uniform_costs_info(self):
+        """{cells, levels, block, lds_bytes, device_ms} of the last uniform_costs on this plan (smashx_uniform_costs_info)."""
+        info, ms = (C.c_int * 4)(), C.c_float(0.0)
+        _lib.check(_lib.lib().smashx_uniform_costs_info(self._h, info, C.byref(ms)))
+        return {"cells": info[0], "levels": info[1], "block": info[2], "lds_bytes": info[3], "device_ms": float(ms.value)}
+
     # -- interception capacity ---------------------------------------------------------------------
     def adjust_interception(self, day_index, ci=None):
         """adjust_interception_store (mw_interception_store.f90:19-160) on the plan's resident forcing: day_index (nt) is the 1-based
@@ -701,6 +719,15 @@ def multiple_run(setup, mesh, input_data, parameters, states, sample, return_qsi
     check_multiple_run(setup.structure, mesh.ng, setup.ntime_step, mat, ind)
     s = _solver_for(setup, mesh, input_data)
     return s.multiple_run(parameters, states, mat, ind, return_qsim=return_qsim)
+
+
+def uniform_costs(setup, mesh, input_data, parameters, states, sample, ind_parameters_states, res_cost=None):
+    """The cost of every column of sample (nfields, S) -- spatially uniform values of the fields ind_parameters_states, 1-based into
+    the stacked md_constant order -- on the catchment-resident kernel: what compute_multiple_run returns as res_cost, for the few
+    candidates of a uniform calibration on a small catchment (smashx_uniform_costs; SmashxError(E_UNSUPPORTED) beyond its limits)."""
+    sample, ind = check_multiple_run(setup.structure, mesh.ng, setup.ntime_step, sample, ind_parameters_states, res_cost)
+    s = _solver_for(setup, mesh, input_data)
+    return s.uniform_costs(parameters, states, sample, ind, res_cost=res_cost)
 
 
 # ---- interception capacity: mw_interception_store::adjust_interception_store (mw_interception_store.f90:19-160) -------------------
