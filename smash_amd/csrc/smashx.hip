@@ -29,6 +29,7 @@
 #include "sx_hyperhost.h"
 #include "sx_annmap.h"
 #include "sx_annhost.h"
+#include "sx_samplehost.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -450,47 +451,46 @@ struct smashx_plan {
         int* d_list = nullptr; float *d_dl = nullptr, *d_d2l = nullptr; SxPiGauge* d_gauges = nullptr;
         float *d_state = nullptr, *d_out = nullptr; int* d_flag = nullptr;
     } pi;
-    // hyper maps on the device (smashx_hyper_*, sx_hypermap.h): the descriptors in plan-cell order and the host copy they are compared
-    // with, the plan cells in the order of the adjoint's sums, the hyper matrices (nh, 24), the staging rows of a span and the chains
-    struct Hyper {
-        bool have = false, mapped = false;       // descriptors set; a smashx_hyper_upload has run with them
-        bool options = false;                    // smashx_set_options has been called (the plan's default options carry no bounds)
-        int mapping = 0, nd = 0, nh = 0;
+    // what the two regional maps (smashx_hyper_*, smashx_ann_*) hold alike: the descriptors in plan-cell order, the host copy they are
+    // compared with, the plan cells in the order of the adjoint's sums (set_descriptors); events and times of map and gradient (timed_*)
+    struct Descriptors {
+        bool have = false; int nd = 0;
         std::vector<float> h_desc;               // [nd][n], as gathered
-        float* d_desc = nullptr; size_t desc_cap = 0;
-        int* d_order = nullptr;
+        float* d_desc = nullptr; size_t desc_cap = 0; int* d_order = nullptr;
+    };
+    struct MapTiming { hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; float map_ms = 0.f, grad_ms = 0.f; };
+    // hyper maps on the device (smashx_hyper_*, sx_hypermap.h): the descriptors, the hyper matrices (nh, 24), the staging rows of a span
+    // and the chains
+    struct Hyper {
+        Descriptors dsc; MapTiming tm;
+        bool mapped = false;                     // a smashx_hyper_upload has run with the descriptors held
+        bool options = false;                    // smashx_set_options has been called (the plan's default options carry no bounds)
+        int mapping = 0, nh = 0;
         float* d_h = nullptr; size_t h_cap = 0;
         float* d_terms = nullptr; size_t terms_cap = 0;
         float* d_sums = nullptr; size_t sums_cap = 0;
         float* d_tmp = nullptr;                  // a cell vector for the fields without a slot (smashx_hyper_fields)
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
         int nchain = 0, span = 0;
-        float map_ms = 0.f, grad_ms = 0.f;
     } hyp;
-    // the ANN regionalisation on the device (smashx_ann_*, sx_annmap.h): its own descriptors in plan-cell order with the host copy they
-    // are compared with, the graph, the packed weights, cell vectors for the control fields without a slot, the staging rows of a span
+    // the ANN regionalisation on the device (smashx_ann_*, sx_annmap.h): its own descriptors, the graph, the packed weights, cell vectors
+    // for the control fields without a slot, the staging rows of a span
     struct Ann {
-        bool have_desc = false, have_net = false, mapped = false;    // mapped: a smashx_ann_upload has run with the descriptors and the net held
-        int nd = 0;
-        std::vector<float> h_desc;               // [nd][n], as gathered
-        float* d_desc = nullptr; size_t desc_cap = 0;
-        int* d_order = nullptr;
+        Descriptors dsc; MapTiming tm;
+        bool have_net = false, mapped = false;   // mapped: a smashx_ann_upload has run with the descriptors and the net held
         SxAnnNet net{};
         int field[SX_ANN_MAXCV] = {0};
         double* d_w = nullptr; size_t w_cap = 0;
         float* d_extra = nullptr; size_t extra_cap = 0;
         double* d_terms = nullptr; size_t terms_cap = 0;
         double* d_sums = nullptr; size_t sums_cap = 0;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
         int span = 0;
-        float map_ms = 0.f, grad_ms = 0.f;
     } ann;
     struct Ens {
         bool tables = false;
         int nlevels = 0; std::vector<int> level_begin;
         int *d_up = nullptr, *d_upn = nullptr, *d_order = nullptr, *d_gauge_k = nullptr;
         float *base = nullptr, *plane = nullptr;
-        float *sample = nullptr, *state = nullptr, *qt = nullptr, *qg = nullptr, *gj = nullptr, *med = nullptr, *cost = nullptr, *qout = nullptr;
+        float *sample = nullptr, *state = nullptr, *qt = nullptr, *qg = nullptr, *gj = nullptr, *cost = nullptr, *qout = nullptr;
         size_t cap_sample = 0, cap_state = 0, cap_qt = 0, cap_qg = 0, cap_gj = 0, cap_cost = 0, cap_qout = 0;
         hipEvent_t ev_a = nullptr, ev_b = nullptr;
         int info[4] = {0, 0, 0, 0};      // batch size, time chunk, batches, chunks per batch of the last call
@@ -543,6 +543,16 @@ int set_device(const smashx_plan* p) {
     if (p->cfg.device >= 0) HIPCHK(hipSetDevice(p->cfg.device));
     return 0;
 }
+// a device buffer that only grows: at least `need` elements behind *buf, *cap of them held
+template <class T> int dev_grow(smashx_plan* p, T** buf, size_t* cap, size_t need) {
+    if (*cap >= need) return 0;
+    if (*buf) p->dfree(*buf);
+    *buf = nullptr; *cap = 0;
+    int rc = p->dmalloc(buf, need); if (rc) return rc;
+    *cap = need;
+    return 0;
+}
+int env_int(const char* name) { const char* e = getenv(name); return e ? std::max(0, atoi(e)) : 0; }      // a length from the environment; 0: none
 
 // ---- fields (sx_fields.h) on this plan ------------------------------------------------------------------------------------------
 static_assert(SX_NPSLOTS == SX_ENS_NP && SX_NSSLOTS == SX_ENS_NS, "the ensemble kernels number the slots like sx_fields.h");
@@ -1189,8 +1199,8 @@ int smashx_plan_destroy(smashx_plan* p) {
     if (p->ev_j) (void)hipEventDestroy(p->ev_j);
     if (p->ens.ev_a) (void)hipEventDestroy(p->ens.ev_a);
     if (p->ens.ev_b) (void)hipEventDestroy(p->ens.ev_b);
-    for (hipEvent_t e : p->hyp.ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : p->ann.ev) if (e) (void)hipEventDestroy(e);
+    for (const smashx_plan::MapTiming* t : {&p->hyp.tm, &p->ann.tm})
+        for (hipEvent_t e : t->ev) if (e) (void)hipEventDestroy(e);
     delete p;
     return 0;
 }
@@ -2711,111 +2721,126 @@ int ens_tables(smashx_plan* p) {
     return 0;
 }
 
-int ens_grow(smashx_plan* p, float** buf, size_t* cap, size_t need) {
-    if (*cap >= need) return 0;
-    if (*buf) p->dfree(*buf);
-    *buf = nullptr; *cap = 0;
-    int rc = p->dmalloc(buf, need); if (rc) return rc;
-    *cap = need;
-    return 0;
-}
+static_assert(SX_ENS_NP + SX_ENS_NS == SX_NSLOTS, "the ensemble's slots are the slots of sx_fields.h");
+// The frame of the two sample paths (smashx_multiple_run, smashx_uniform_costs; host side: sx_samplehost.h).  open: the checks and
+// refusals both share, the forest; base: the base fields; arrays: the buffers both need and SxEnsArrays; per batch begin (ev_a, the
+// sample up), the path's own launches, costs, end (ev_b, the path's own copies, one synchronisation, the costs into dst).
+struct SampleBatches {
+    smashx_plan* p = nullptr; std::string who;
+    int nfields = 0, nsamples = 0; const float* sample = nullptr;
+    int smap[SX_NSLOTS], used_states = 0;          // used_states: bit i = the structure uses state slot i (the ensemble path's init)
+    int SP = 0, nbatch = 0, s0 = 0, cnt = 0;       // s0, cnt: first sample and samples of the batch begun
+    float* ms = nullptr;                           // device time of the call, summed over the batches
+    SxEnsArrays E{}; SxCostArgs C{};
+    std::vector<float> hs, hc;
 
-int ens_env(const char* name) { const char* e = getenv(name); return e ? std::max(0, atoi(e)) : 0; }
+    // reference_call: the reference's routine that never sets denormalize_forward; limit_msg(n): the refusal of more than max_cells
+    int open(smashx_plan* plan, const char* name, const char* reference_call, const smashx_parameters* params, const smashx_states* states,
+             int nf, const int* ind, const float* smp, int ns, const float* res_cost, long max_cells, std::string (*limit_msg)(int)) {
+        p = plan; who = name; nfields = nf; nsamples = ns; sample = smp;
+        if (!p || !params || !states || !res_cost) return fail(SMASHX_E_ARG, who + ": null argument (plan, parameters, states, res_cost)");
+        if (nsamples < 1) return fail(SMASHX_E_ARG, who + ": nsamples < 1");
+        if (nfields < 0 || nfields > SX_NFIELDS || (nfields > 0 && (!ind || !sample))) return fail(SMASHX_E_ARG, who + ": bad nfields / null index list or sample");
+        const std::string why = sx_sh_field_map(p->st, nfields, ind, smap);
+        if (!why.empty()) return fail(SMASHX_E_ARG, who + ": " + why);
+        if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, who + ": denormalize_forward is not supported (the reference's " + reference_call + " never sets it)");
+        if (p->opt.wjreg != 0.f && p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, who + ": wjreg with a regulariser (jreg_fun) is not supported");
+        if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, who + ": a tiled plan (tile / owner_mask) is not supported");
+        if (wants_signature(p->opt)) return fail(SMASHX_E_UNSUPPORTED, who + ": signature-based jobs_fun are not built into the ensemble cost");
+        if (p->n > max_cells) return fail(SMASHX_E_UNSUPPORTED, who + ": " + limit_msg(p->n));
+        if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
+        const int rc = set_device(p);
+        return rc ? rc : ens_tables(p);
+    }
+    // base fields in cell order; a sampled field needs no base
+    int base(const smashx_parameters* params, const smashx_states* states) {
+        int rc = close_forcing(p); if (rc) return rc;
+        auto& X = p->ens;
+        for (int slot = 0; slot < SX_NSLOTS; ++slot) {
+            const bool isp = !sx_slot_is_state(slot);
+            const int f = sx_slot_field(p->st, slot);
+            if (f < 0) continue;
+            if (!isp) used_states |= 1 << (slot - SX_NPSLOTS);
+            if (smap[slot] >= 0) continue;
+            const float* h = host_plane(params, states, f);
+            if (!h) return fail(SMASHX_E_ARG, who + ": a " + (isp ? "parameter" : "state") + " field the structure uses is NULL and not sampled");
+            HIPCHK(hipMemcpyAsync(X.plane, h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, p->stream));
+            hipLaunchKernelGGL(k_gather, dim3((p->n + 255) / 256), dim3(256), 0, p->stream, X.base + (size_t)slot * p->npad, X.plane, p->d_cell_flat, p->n);
+        }
+        return 0;
+    }
+    // batches of sp columns, time chunks of tc steps: the buffers both paths need, and what of SxEnsArrays lives in them
+    int arrays(int sp, int tc, float* device_ms) {
+        auto& X = p->ens;
+        const size_t sSP = (size_t)sp, ng1 = (size_t)std::max(p->ng, 1);
+        int rc;
+        SP = sp; nbatch = (nsamples + SP - 1) / SP; ms = device_ms;
+        if ((rc = dev_grow(p, &X.sample, &X.cap_sample, (size_t)std::max(nfields, 1) * sSP)) || (rc = dev_grow(p, &X.qg, &X.cap_qg, ng1 * p->nt * sSP)) ||
+            (rc = dev_grow(p, &X.gj, &X.cap_gj, 2 * ng1 * sSP)) || (rc = dev_grow(p, &X.cost, &X.cap_cost, sSP))) return rc;
+        E.n = p->n; E.npad = p->npad; E.SP = SP; E.Tc = tc;
+        for (int i = 0; i < SX_NSLOTS; ++i) E.smap[i] = smap[i];
+        E.base = X.base; E.sample = X.sample; E.up = X.d_up; E.upn = X.d_upn; E.order = X.d_order;
+        E.qg = X.qg; E.gauge_k = X.d_gauge_k; E.gj = X.gj; E.med = X.gj + ng1 * sSP; E.cost = X.cost;
+        C = cost_args(p, 0.f);
+        hs.resize((size_t)std::max(nfields, 1) * sSP); hc.resize(sSP);
+        return 0;
+    }
+    int begin(int bi) {
+        if (bi == 0) *ms = 0.f;
+        s0 = bi * SP; cnt = std::min(SP, nsamples - s0);
+        sx_sh_stage(sample, nfields, nsamples, s0, SP, hs.data());
+        HIPCHK(hipEventRecord(p->ens.ev_a, p->stream));
+        if (nfields > 0) HIPCHK(hipMemcpyAsync(p->ens.sample, hs.data(), (size_t)nfields * SP * 4, hipMemcpyHostToDevice, p->stream));
+        return 0;
+    }
+    int costs() {          // of qg [g][t][SP]; without a gauge the cost is 0
+        if (p->ng == 0) return 0;
+        hipLaunchKernelGGL(sx_k_ens_cost_gauge, dim3(SP / 64, p->ng), dim3(64), 0, p->stream, C, E);
+        hipLaunchKernelGGL(sx_k_ens_cost_final, dim3(SP / 64), dim3(64), 0, p->stream, C, E);
+        HIPCHK(hipMemcpyAsync(hc.data(), p->ens.cost, (size_t)cnt * 4, hipMemcpyDeviceToHost, p->stream));
+        return 0;
+    }
+    int end(float* dst, void* series = nullptr, const void* d_series = nullptr, size_t bytes = 0) {     // series: a copy of the path's own
+        HIPCHK(hipEventRecord(p->ens.ev_b, p->stream));
+        if (bytes) HIPCHK(hipMemcpyAsync(series, d_series, bytes, hipMemcpyDeviceToHost, p->stream));
+        HIPCHK(hipStreamSynchronize(p->stream));
+        HIPCHK(hipGetLastError());
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, p->ens.ev_a, p->ens.ev_b) == hipSuccess) *ms += t;
+        // cost = jobs + wjreg * jreg with jreg = 0 (mwd_cost.f90:300), as smashx_download forms it
+        for (int c = 0; c < cnt; ++c) dst[s0 + c] = (p->ng > 0 ? hc[c] : 0.f) + p->opt.wjreg * 0.f;
+        return 0;
+    }
+};
 }  // namespace
 
 int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const smashx_states* states, int nfields,
                         const int* ind, const float* sample, int nsamples, float* res_cost, float* res_qsim) {
-    if (!p || !params || !states || !res_cost) return fail(SMASHX_E_ARG, "smashx_multiple_run: null argument (plan, parameters, states, res_cost)");
-    if (nsamples < 1) return fail(SMASHX_E_ARG, "smashx_multiple_run: nsamples < 1");
-    if (nfields < 0 || nfields > SMASHX_GNP + SMASHX_GNS || (nfields > 0 && (!ind || !sample))) return fail(SMASHX_E_ARG, "smashx_multiple_run: bad nfields / null index list or sample");
-    const int st = p->st;
-    int smap[SX_ENS_NP + SX_ENS_NS];
-    for (int& v : smap) v = -1;
-    for (int j = 0; j < nfields; ++j) {
-        const int f = ind[j];
-        if (f < 1 || f > SMASHX_GNP + SMASHX_GNS) return fail(SMASHX_E_ARG, "smashx_multiple_run: ind_parameters_states[" + std::to_string(j) + "] = " + std::to_string(f) + " is outside 1..24");
-        const int slot = sx_field_slot(st, f - 1);
-        if (slot < 0) return fail(SMASHX_E_ARG, "smashx_multiple_run: field " + std::to_string(f) + " is not used by the structure");
-        if (smap[slot] >= 0) return fail(SMASHX_E_ARG, "smashx_multiple_run: field " + std::to_string(f) + " is listed twice");
-        smap[slot] = j;
-    }
-    if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: denormalize_forward is not supported (the reference's multiple_run never sets it)");
-    if (p->opt.wjreg != 0.f && p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: wjreg with a regulariser (jreg_fun) is not supported");
-    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: a tiled plan (tile / owner_mask) is not supported");
-    if (wants_signature(p->opt)) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: signature-based jobs_fun are not built into the ensemble cost");
-    if (p->n > 65535 * SX_ENS_CELLS) return fail(SMASHX_E_UNSUPPORTED, "smashx_multiple_run: more than 262140 active cells");
-    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
-    int rc = set_device(p); if (rc) return rc;
-    if ((rc = ens_tables(p))) return rc;
+    SampleBatches B;
+    int rc = B.open(p, "smashx_multiple_run", "multiple_run", params, states, nfields, ind, sample, nsamples, res_cost, 65535L * SX_ENS_CELLS,
+                    [](int) { return std::string("more than 262140 active cells"); });
+    if (rc || (rc = B.base(params, states))) return rc;
     auto& X = p->ens;
     hipStream_t sV = p->stream;
-    if ((rc = close_forcing(p))) return rc;
-    const int n = p->n, nt = p->nt, ng = p->ng;
-
-    // base fields in cell order; a sampled field needs no base
-    const dim3 b256(256), gk((n + 255) / 256);
-    int used_states = 0;
-    for (int slot = 0; slot < SX_ENS_NP + SX_ENS_NS; ++slot) {
-        const bool isp = !sx_slot_is_state(slot);
-        const int f = sx_slot_field(st, slot);
-        if (f < 0) continue;
-        if (!isp) used_states |= 1 << (slot - SX_ENS_NP);
-        if (smap[slot] >= 0) continue;
-        const float* h = host_plane(params, states, f);
-        if (!h) return fail(SMASHX_E_ARG, std::string("smashx_multiple_run: a ") + (isp ? "parameter" : "state") + " field the structure uses is NULL and not sampled");
-        HIPCHK(hipMemcpyAsync(X.plane, h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
-        hipLaunchKernelGGL(k_gather, gk, b256, 0, sV, X.base + (size_t)slot * p->npad, X.plane, p->d_cell_flat, n);
-    }
+    const int st = p->st, n = p->n, nt = p->nt, ng = p->ng;
 
     // batch size and time chunk
-    const int SPall = (nsamples + 63) / 64 * 64;
-    const int env_b = ens_env("SMASHX_ENS_BATCH"), env_c = ens_env("SMASHX_ENS_CHUNK");
-    int SP = std::min(SPall, env_b > 0 ? (env_b + 63) / 64 * 64 : 16384);
-    int Tc = std::min(nt, env_c > 0 ? env_c : 32768);
-    {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        const double held = 4.0 * (double)(X.cap_qt + X.cap_qg + X.cap_qout + X.cap_state);      // what a previous call already holds can be reused
-        const double budget = std::min(0.6 * ((double)fr + held), 24.0 * 1024 * 1024 * 1024);
-        auto need = [&](int sp, int tc) {
-            return 4.0 * sp * ((double)n * tc + (double)nt * std::max(ng, 1) * (res_qsim ? 2 : 1) + 5.0 * n + 64.0);
-        };
-        while (need(SP, Tc) > budget) {
-            if (env_c == 0 && Tc > 256) Tc = (Tc + 1) / 2;
-            else if (env_b == 0 && SP > 64) SP = (SP / 2 + 63) / 64 * 64;
-            else break;      // forced lengths that do not fit: the allocation below says so
-        }
-    }
-    const int nbatch = (nsamples + SP - 1) / SP, nchunk = (nt + Tc - 1) / Tc;
+    int SP = 0, Tc = 0;
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    sx_sh_budget(n, nt, ng, nsamples, res_qsim != nullptr, env_int("SMASHX_ENS_BATCH"), env_int("SMASHX_ENS_CHUNK"), (double)fr,
+                 4.0 * (double)(X.cap_qt + X.cap_qg + X.cap_qout + X.cap_state), &SP, &Tc);      // what a previous call already holds can be reused
+    const int nchunk = (nt + Tc - 1) / Tc;
     const size_t sSP = (size_t)SP;
-    if ((rc = ens_grow(p, &X.sample, &X.cap_sample, (size_t)std::max(nfields, 1) * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.state, &X.cap_state, (size_t)SX_ENS_NS * n * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.qt, &X.cap_qt, (size_t)n * Tc * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.qg, &X.cap_qg, (size_t)std::max(ng, 1) * nt * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.gj, &X.cap_gj, (size_t)2 * std::max(ng, 1) * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.cost, &X.cap_cost, sSP))) return rc;
-    if (res_qsim && ng > 0 && (rc = ens_grow(p, &X.qout, &X.cap_qout, (size_t)ng * nt * sSP))) return rc;
-
-    SxEnsArrays E{};
-    E.n = n; E.npad = p->npad; E.SP = SP; E.Tc = Tc;
-    E.base = X.base; E.sample = X.sample;
-    for (int i = 0; i < SX_ENS_NP + SX_ENS_NS; ++i) E.smap[i] = smap[i];
-    E.state = X.state; E.qt = X.qt; E.up = X.d_up; E.upn = X.d_upn; E.order = X.d_order;
-    E.qg = X.qg; E.gauge_k = X.d_gauge_k; E.gj = X.gj; E.med = X.gj + (size_t)std::max(ng, 1) * sSP; E.cost = X.cost; E.qout = X.qout;
-    const SxCostArgs C = cost_args(p, 0.f);
-    const dim3 b64(64), bV(64, SX_ENS_CELLS), gS(SP / 64);
-    const dim3 gV(SP / 64, (n + SX_ENS_CELLS - 1) / SX_ENS_CELLS);
-    std::vector<float> hs((size_t)std::max(nfields, 1) * sSP), hc(sSP);
-    X.device_ms = 0.f;
-    for (int bi = 0; bi < nbatch; ++bi) {
-        const int s0 = bi * SP, cnt = std::min(SP, nsamples - s0);
-        // sample(nfields, S) column-major -> [field][column]; the columns past the batch's last sample repeat it (whole wavefronts
-        // of ordinary values: nothing of them is ever copied out)
-        for (int j = 0; j < nfields; ++j)
-            for (int c = 0; c < SP; ++c) hs[(size_t)j * sSP + c] = sample[(size_t)j + (size_t)nfields * (s0 + std::min(c, cnt - 1))];
-        HIPCHK(hipEventRecord(X.ev_a, sV));
-        if (nfields > 0) HIPCHK(hipMemcpyAsync(X.sample, hs.data(), (size_t)nfields * sSP * 4, hipMemcpyHostToDevice, sV));
-        hipLaunchKernelGGL(sx_k_ens_init_states, dim3(SP / 64, std::min(n, 65535)), b64, 0, sV, E, used_states);
+    if ((rc = B.arrays(SP, Tc, &X.device_ms))) return rc;
+    if ((rc = dev_grow(p, &X.state, &X.cap_state, (size_t)SX_ENS_NS * n * sSP)) || (rc = dev_grow(p, &X.qt, &X.cap_qt, (size_t)n * Tc * sSP))) return rc;
+    if (res_qsim && ng > 0 && (rc = dev_grow(p, &X.qout, &X.cap_qout, (size_t)ng * nt * sSP))) return rc;
+    SxEnsArrays& E = B.E;
+    E.state = X.state; E.qt = X.qt; E.qout = X.qout;
+    const dim3 b64(64), bV(64, SX_ENS_CELLS), gV(SP / 64, (n + SX_ENS_CELLS - 1) / SX_ENS_CELLS);
+    for (int bi = 0; bi < B.nbatch; ++bi) {
+        if ((rc = B.begin(bi))) return rc;
+        hipLaunchKernelGGL(sx_k_ens_init_states, dim3(SP / 64, std::min(n, 65535)), b64, 0, sV, E, B.used_states);
         for (int c = 0; c < nchunk; ++c) {
             const int t0 = c * Tc, T = std::min(Tc, nt - t0);
             switch (st) {
@@ -2833,23 +2858,12 @@ int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const s
             }
             if (ng > 0) hipLaunchKernelGGL(sx_k_ens_gauges, dim3(SP / 64, std::min(T, 65535), ng), b64, 0, sV, E, nt, t0, T);
         }
-        if (ng > 0) {
-            hipLaunchKernelGGL(sx_k_ens_cost_gauge, dim3(SP / 64, ng), b64, 0, sV, C, E);
-            hipLaunchKernelGGL(sx_k_ens_cost_final, gS, b64, 0, sV, C, E);
-            HIPCHK(hipMemcpyAsync(hc.data(), X.cost, (size_t)cnt * 4, hipMemcpyDeviceToHost, sV));
-            if (res_qsim) hipLaunchKernelGGL(sx_k_ens_qsim_out, dim3(SP / 64, std::min(nt, 65535)), b64, 0, sV, E, ng, nt);
-        }
-        HIPCHK(hipEventRecord(X.ev_b, sV));
-        if (res_qsim && ng > 0)
-            HIPCHK(hipMemcpyAsync(res_qsim + (size_t)s0 * nt * ng, X.qout, (size_t)cnt * nt * ng * 4, hipMemcpyDeviceToHost, sV));
-        HIPCHK(hipStreamSynchronize(sV));
-        HIPCHK(hipGetLastError());
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, X.ev_a, X.ev_b) == hipSuccess) X.device_ms += ms;
-        // cost = jobs + wjreg * jreg with jreg = 0 (mwd_cost.f90:300), as smashx_download forms it
-        for (int c = 0; c < cnt; ++c) res_cost[s0 + c] = (ng > 0 ? hc[c] : 0.f) + p->opt.wjreg * 0.f;
+        if ((rc = B.costs())) return rc;
+        const bool series = res_qsim && ng > 0;
+        if (series) hipLaunchKernelGGL(sx_k_ens_qsim_out, dim3(SP / 64, std::min(nt, 65535)), b64, 0, sV, E, ng, nt);
+        if ((rc = B.end(res_cost, series ? res_qsim + (size_t)B.s0 * nt * ng : nullptr, X.qout, series ? (size_t)B.cnt * nt * ng * 4 : 0))) return rc;
     }
-    X.info[0] = SP; X.info[1] = Tc; X.info[2] = nbatch; X.info[3] = nchunk;
+    X.info[0] = SP; X.info[1] = Tc; X.info[2] = B.nbatch; X.info[3] = nchunk;
     return 0;
 }
 
@@ -2938,97 +2952,35 @@ int res_launch(smashx_plan* p, const SxEnsArrays& E, const SxResTables& R, int S
 
 int smashx_uniform_costs(smashx_plan* p, const smashx_parameters* params, const smashx_states* states, int nfields,
                          const int* ind, const float* sample, int nsamples, float* res_cost) {
-    if (!p || !params || !states || !res_cost) return fail(SMASHX_E_ARG, "smashx_uniform_costs: null argument (plan, parameters, states, res_cost)");
-    if (nsamples < 1) return fail(SMASHX_E_ARG, "smashx_uniform_costs: nsamples < 1");
-    if (nfields < 0 || nfields > SMASHX_GNP + SMASHX_GNS || (nfields > 0 && (!ind || !sample))) return fail(SMASHX_E_ARG, "smashx_uniform_costs: bad nfields / null index list or sample");
-    const int st = p->st;
-    int smap[SX_ENS_NP + SX_ENS_NS];
-    for (int& v : smap) v = -1;
-    for (int j = 0; j < nfields; ++j) {
-        const int f = ind[j];
-        if (f < 1 || f > SMASHX_GNP + SMASHX_GNS) return fail(SMASHX_E_ARG, "smashx_uniform_costs: ind_parameters_states[" + std::to_string(j) + "] = " + std::to_string(f) + " is outside 1..24");
-        const int slot = sx_field_slot(st, f - 1);
-        if (slot < 0) return fail(SMASHX_E_ARG, "smashx_uniform_costs: field " + std::to_string(f) + " is not used by the structure");
-        if (smap[slot] >= 0) return fail(SMASHX_E_ARG, "smashx_uniform_costs: field " + std::to_string(f) + " is listed twice");
-        smap[slot] = j;
-    }
-    if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: denormalize_forward is not supported (the reference's optimize_sbs never sets it)");
-    if (p->opt.wjreg != 0.f && p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: wjreg with a regulariser (jreg_fun) is not supported");
-    if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: a tiled plan (tile / owner_mask) is not supported");
-    if (wants_signature(p->opt)) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: signature-based jobs_fun are not built into the ensemble cost");
-    if (p->n > SX_RES_MAXCELLS) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: " + std::to_string(p->n) + " active cells, the resident kernel holds one cell per thread and at most " + std::to_string(SX_RES_MAXCELLS));
-    if (!p->have_forcing) return fail(SMASHX_E_STATE, "forcing not set");
-    int rc = set_device(p); if (rc) return rc;
-    if ((rc = ens_tables(p))) return rc;
-    if ((rc = res_tables(p))) return rc;
+    SampleBatches B;
+    int rc = B.open(p, "smashx_uniform_costs", "optimize_sbs", params, states, nfields, ind, sample, nsamples, res_cost, SX_RES_MAXCELLS,
+                    [](int n) { return std::to_string(n) + " active cells, the resident kernel holds one cell per thread and at most " + std::to_string(SX_RES_MAXCELLS); });
+    if (rc || (rc = res_tables(p))) return rc;
     auto& X = p->ens;
     if (X.res_state == 2) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: " + X.res_refusal);
-    hipStream_t sV = p->stream;
-    if ((rc = close_forcing(p))) return rc;
-    const int n = p->n, nt = p->nt, ng = p->ng;
-
-    // base fields in cell order; a sampled field needs no base
-    const dim3 b256(256), gk((n + 255) / 256);
-    for (int slot = 0; slot < SX_ENS_NP + SX_ENS_NS; ++slot) {
-        const bool isp = !sx_slot_is_state(slot);
-        const int f = sx_slot_field(st, slot);
-        if (f < 0 || smap[slot] >= 0) continue;
-        const float* h = host_plane(params, states, f);
-        if (!h) return fail(SMASHX_E_ARG, std::string("smashx_uniform_costs: a ") + (isp ? "parameter" : "state") + " field the structure uses is NULL and not sampled");
-        HIPCHK(hipMemcpyAsync(X.plane, h, (size_t)p->n2 * 4, hipMemcpyHostToDevice, sV));
-        hipLaunchKernelGGL(k_gather, gk, b256, 0, sV, X.base + (size_t)slot * p->npad, X.plane, p->d_cell_flat, n);
-    }
-
-    const int SP = std::min((nsamples + 63) / 64 * 64, 16384);       // samples per batch: one launch of SP workgroups
-    const int nbatch = (nsamples + SP - 1) / SP;
-    const size_t sSP = (size_t)SP;
-    if ((rc = ens_grow(p, &X.sample, &X.cap_sample, (size_t)std::max(nfields, 1) * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.qg, &X.cap_qg, (size_t)std::max(ng, 1) * nt * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.gj, &X.cap_gj, (size_t)2 * std::max(ng, 1) * sSP))) return rc;
-    if ((rc = ens_grow(p, &X.cost, &X.cap_cost, sSP))) return rc;
-
-    SxEnsArrays E{};
-    E.n = n; E.npad = p->npad; E.SP = SP; E.Tc = nt;
-    E.base = X.base; E.sample = X.sample;
-    for (int i = 0; i < SX_ENS_NP + SX_ENS_NS; ++i) E.smap[i] = smap[i];
-    E.up = X.d_up; E.upn = X.d_upn; E.order = X.d_order;
-    E.qg = X.qg; E.gauge_k = X.d_gauge_k; E.gj = X.gj; E.med = X.gj + (size_t)std::max(ng, 1) * sSP; E.cost = X.cost;
+    if ((rc = B.base(params, states))) return rc;
+    // samples per batch: one launch of as many workgroups as the batch has samples
+    if ((rc = B.arrays(std::min((nsamples + 63) / 64 * 64, 16384), p->nt, &X.res_ms))) return rc;
     SxResTables R{};
     R.nlevels = X.nlevels; R.cell = X.r_cell; R.level = X.r_level; R.upline = X.r_upline; R.upn = X.r_upn; R.ownline = X.r_ownline;
     R.gfirst = X.r_gfirst; R.gnext = X.r_gnext;
-    const SxCostArgs C = cost_args(p, 0.f);
-    const dim3 b64(64), gS(SP / 64);
-    std::vector<float> hs((size_t)std::max(nfields, 1) * sSP), hc(sSP), out(nsamples);
-    X.res_ms = 0.f;
-    for (int bi = 0; bi < nbatch; ++bi) {
-        const int s0 = bi * SP, cnt = std::min(SP, nsamples - s0);
-        for (int j = 0; j < nfields; ++j)
-            for (int c = 0; c < SP; ++c) hs[(size_t)j * sSP + c] = sample[(size_t)j + (size_t)nfields * (s0 + std::min(c, cnt - 1))];
-        HIPCHK(hipEventRecord(X.ev_a, sV));
-        if (nfields > 0) HIPCHK(hipMemcpyAsync(X.sample, hs.data(), (size_t)nfields * sSP * 4, hipMemcpyHostToDevice, sV));
-        if (ng > 0) {       // without a gauge the cost is 0 and nothing has to run
-            switch (st) {
-                case 1: rc = res_launch<1>(p, E, R, cnt, sV); break;
-                case 2: rc = res_launch<2>(p, E, R, cnt, sV); break;
-                case 3: rc = res_launch<3>(p, E, R, cnt, sV); break;
-                case 4: rc = res_launch<4>(p, E, R, cnt, sV); break;
-                default: rc = res_launch<5>(p, E, R, cnt, sV); break;
+    std::vector<float> out(nsamples);
+    for (int bi = 0; bi < B.nbatch; ++bi) {
+        if ((rc = B.begin(bi))) return rc;
+        if (p->ng > 0) {    // without a gauge the cost is 0 and nothing has to run
+            switch (p->st) {
+                case 1: rc = res_launch<1>(p, B.E, R, B.cnt, p->stream); break;
+                case 2: rc = res_launch<2>(p, B.E, R, B.cnt, p->stream); break;
+                case 3: rc = res_launch<3>(p, B.E, R, B.cnt, p->stream); break;
+                case 4: rc = res_launch<4>(p, B.E, R, B.cnt, p->stream); break;
+                default: rc = res_launch<5>(p, B.E, R, B.cnt, p->stream); break;
             }
             if (rc) return rc;
-            hipLaunchKernelGGL(sx_k_ens_cost_gauge, dim3(SP / 64, ng), b64, 0, sV, C, E);
-            hipLaunchKernelGGL(sx_k_ens_cost_final, gS, b64, 0, sV, C, E);
-            HIPCHK(hipMemcpyAsync(hc.data(), X.cost, (size_t)cnt * 4, hipMemcpyDeviceToHost, sV));
         }
-        HIPCHK(hipEventRecord(X.ev_b, sV));
-        HIPCHK(hipStreamSynchronize(sV));
-        HIPCHK(hipGetLastError());
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, X.ev_a, X.ev_b) == hipSuccess) X.res_ms += ms;
-        // cost = jobs + wjreg * jreg with jreg = 0 (mwd_cost.f90:300), as smashx_download forms it
-        for (int c = 0; c < cnt; ++c) out[s0 + c] = (ng > 0 ? hc[c] : 0.f) + p->opt.wjreg * 0.f;
+        if ((rc = B.costs()) || (rc = B.end(out.data()))) return rc;
     }
     for (int i = 0; i < nsamples; ++i) res_cost[i] = out[i];      // only a complete call writes res_cost
-    X.res_info[0] = n; X.res_info[1] = X.nlevels; X.res_info[2] = X.res_block; X.res_info[3] = (int)(X.res_lds + X.res_static);
+    X.res_info[0] = p->n; X.res_info[1] = X.nlevels; X.res_info[2] = X.res_block; X.res_info[3] = (int)(X.res_lds + X.res_static);
     return 0;
 }
 
@@ -3039,12 +2991,72 @@ int smashx_uniform_costs_info(const smashx_plan* p, int info[4], float* device_m
     return 0;
 }
 
+// ---- what the two regional maps (smashx_hyper_*, smashx_ann_*) do alike: descriptors, timed upload and gradient, read-back ---------------
+namespace {
+// the descriptors gathered to plan-cell order and, on first use, the order of the adjoint's sums.  They go up, and *changed is set, only
+// when they differ BY BITS from the host copy (a calibration hands the same ones over before every evaluation; NaN == NaN, +0 != -0)
+int set_descriptors(smashx_plan* p, smashx_plan::Descriptors& D, int nd, const float* descriptor, bool* changed) {
+    int rc;
+    std::vector<float> g;
+    sx_hh_gather(descriptor, nd, (size_t)p->n2, p->sch.cell_flat, g);
+    if (!D.d_order && (rc = p->upload_vec(&D.d_order, sx_hh_order(p->sch.cell_flat)))) return rc;
+    *changed = !(D.have && D.nd == nd && g.size() == D.h_desc.size() && (g.empty() || std::memcmp(g.data(), D.h_desc.data(), g.size() * 4) == 0));
+    if (*changed) {
+        if ((rc = dev_grow(p, &D.d_desc, &D.desc_cap, std::max<size_t>(g.size(), 1)))) return rc;
+        if (!g.empty()) HIPCHK(hipMemcpy(D.d_desc, g.data(), g.size() * 4, hipMemcpyHostToDevice));
+        D.h_desc.swap(g);
+    }
+    D.nd = nd; D.have = true;
+    return 0;
+}
+int map_events(smashx_plan::MapTiming& T) { for (hipEvent_t& e : T.ev) if (!e) HIPCHK(hipEventCreate(&e)); return 0; }
+// entry e of a launch of the map / terms kernels: field f in its slot's cell vectors and plane
+void slot_entry(smashx_plan* p, SxHmFields& F, int e, int f, int slot, bool grad) {
+    const SlotVecs V = slot_vecs(p, slot);
+    F.val[e] = V.val; F.start[e] = V.start != V.val ? V.start : nullptr; F.full[e] = p->d_full[f];
+    F.grad[e] = grad ? V.grad : nullptr;
+}
+extern "C++" {
+// ev[0], the map, ev[1], the routing's preparation on the mapped fields, one synchronisation
+template <class Map> int timed_upload(smashx_plan* p, smashx_plan::MapTiming& T, Map&& map) {
+    HIPCHK(hipEventRecord(T.ev[0], p->stream));
+    map();
+    HIPCHK(hipEventRecord(T.ev[1], p->stream));
+    hipLaunchKernelGGL(sx_k_prep_routing, dim3((p->n + 255) / 256), dim3(256), 0, p->stream, p->A);
+    p->jr_ready = false;
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventElapsedTime(&T.map_ms, T.ev[0], T.ev[1]));
+    return 0;
+}
+// ev[2], the sums zeroed, the path's span loop, ev[3], the sums to the host, one synchronisation
+template <class S, class Spans> int timed_gradient(smashx_plan* p, smashx_plan::MapTiming& T, S* d_sums, std::vector<S>& sums, Spans&& spans) {
+    HIPCHK(hipEventRecord(T.ev[2], p->stream));
+    HIPCHK(hipMemsetAsync(d_sums, 0, sums.size() * sizeof(S), p->stream));
+    spans();
+    HIPCHK(hipEventRecord(T.ev[3], p->stream));
+    HIPCHK(hipMemcpyAsync(sums.data(), d_sums, sums.size() * sizeof(S), hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventElapsedTime(&T.grad_ms, T.ev[2], T.ev[3]));
+    return 0;
+}
+}  // extern "C++"
+// a cell vector of the device into the active cells of a caller's plane
+int read_back(smashx_plan* p, const float* src, std::vector<float>& cellv, float* plane) {
+    HIPCHK(hipMemcpyAsync(cellv.data(), src, (size_t)p->n * 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    sx_hh_scatter(cellv.data(), p->sch.cell_flat, plane);
+    return 0;
+}
+}  // namespace
+
 // ---- hyper maps on the device (include/smashx_hyper.h, sx_hypermap.h) ------------------------------------------------------------
 namespace {
 // what every smashx_hyper_* call but set_descriptors refuses, in the order of the header's table
 int hyper_refusal(const smashx_plan* p, const char* who) {
     if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": a tiled plan (an ordered whole-grid sum does not split across parts)");
-    if (!p->hyp.have) return fail(SMASHX_E_STATE, std::string(who) + ": no descriptors set (smashx_hyper_set_descriptors)");
+    if (!p->hyp.dsc.have) return fail(SMASHX_E_STATE, std::string(who) + ": no descriptors set (smashx_hyper_set_descriptors)");
     if (!p->hyp.options) return fail(SMASHX_E_STATE, std::string(who) + ": options not set (the bounds of the maps are those of smashx_set_options)");
     if (p->opt.denormalize_forward) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": denormalize_forward (base_hyper_forward does not know it)");
     if (p->opt.njr > 0) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": a regulariser (hyper_compute_cost: cost = jobs)");
@@ -3056,17 +3068,20 @@ SxHmFields hyper_slot_fields(smashx_plan* p, bool grad) {
     for (int s = 0; s < SX_NSLOTS; ++s) {
         const int f = sx_slot_field(p->st, s);
         if (f < 0) continue;
-        const SlotVecs V = slot_vecs(p, s);
         const int e = F.nf++;
         F.field[e] = f; F.lb[e] = field_lb(p, f); F.w[e] = field_ub(p, f) - field_lb(p, f);
-        F.val[e] = V.val; F.start[e] = V.start != V.val ? V.start : nullptr; F.full[e] = p->d_full[f];
-        F.grad[e] = grad ? V.grad : nullptr;
+        slot_entry(p, F, e, f, s, grad);
     }
     return F;
 }
-int hyper_events(smashx_plan* p) {
-    for (hipEvent_t& e : p->hyp.ev) if (!e) HIPCHK(hipEventCreate(&e));
-    return 0;
+// the fields of F from the hyper matrices and the descriptors the plan holds
+void hyper_map(smashx_plan* p, const SxHmFields& F) {
+    const smashx_plan::Hyper& H = p->hyp;
+    const dim3 b(256), g((p->n + 255) / 256, F.nf);
+    if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
+        hipLaunchKernelGGL(sx_k_hyper_map<true>, g, b, 0, p->stream, F, H.d_h, H.dsc.d_desc, p->d_cell_flat, H.dsc.nd, H.nh, p->n);
+    else
+        hipLaunchKernelGGL(sx_k_hyper_map<false>, g, b, 0, p->stream, F, H.d_h, H.dsc.d_desc, p->d_cell_flat, H.dsc.nd, H.nh, p->n);
 }
 }  // namespace
 
@@ -3075,21 +3090,12 @@ int smashx_hyper_set_descriptors(smashx_plan* p, int mapping, int nd, const floa
     if (const char* why = sx_hh_bad_arguments(mapping, nd)) return fail(SMASHX_E_ARG, why);
     if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_hyper_set_descriptors: a tiled plan (an ordered whole-grid sum does not split across parts)");
     smashx_plan::Hyper& H = p->hyp;
-    if (nd > 0 && !descriptor) { H.have = H.mapped = false; return 0; }
+    if (nd > 0 && !descriptor) { H.dsc.have = H.mapped = false; return 0; }
     int rc = set_device(p); if (rc) return rc;
-    std::vector<float> g;
-    sx_hh_gather(descriptor, nd, (size_t)p->n2, p->sch.cell_flat, g);
-    const int nh = sx_hh_nhyper(mapping, nd);
-    if (!H.d_order && (rc = p->upload_vec(&H.d_order, sx_hh_order(p->sch.cell_flat)))) return rc;
-    const bool same = H.have && H.nd == nd && g == H.h_desc;      // (a calibration hands the same descriptors over before every evaluation)
-    if (!same) {
-        if ((rc = ens_grow(p, &H.d_desc, &H.desc_cap, std::max<size_t>(g.size(), 1)))) return rc;
-        if (!g.empty()) HIPCHK(hipMemcpy(H.d_desc, g.data(), g.size() * 4, hipMemcpyHostToDevice));
-        H.h_desc.swap(g);
-        H.mapped = false;
-    }
-    if (H.mapping != mapping) H.mapped = false;
-    H.mapping = mapping; H.nd = nd; H.nh = nh; H.have = true;
+    bool changed = false;
+    if ((rc = set_descriptors(p, H.dsc, nd, descriptor, &changed))) return rc;
+    if (changed || H.mapping != mapping) H.mapped = false;
+    H.mapping = mapping; H.nh = sx_hh_nhyper(mapping, nd);
     return 0;
 }
 
@@ -3099,23 +3105,11 @@ int smashx_hyper_upload(smashx_plan* p, const float* hyper_parameters, const flo
     if ((rc = set_device(p))) return rc;
     smashx_plan::Hyper& H = p->hyp;
     const int nh = H.nh;
-    if ((rc = ens_grow(p, &H.d_h, &H.h_cap, (size_t)nh * SX_NFIELDS))) return rc;
-    if ((rc = hyper_events(p))) return rc;
+    if ((rc = dev_grow(p, &H.d_h, &H.h_cap, (size_t)nh * SX_NFIELDS)) || (rc = map_events(H.tm))) return rc;
     HIPCHK(hipMemcpyAsync(H.d_h, hyper_parameters, (size_t)nh * SMASHX_GNP * 4, hipMemcpyHostToDevice, p->stream));
     HIPCHK(hipMemcpyAsync(H.d_h + (size_t)nh * SMASHX_GNP, hyper_states, (size_t)nh * SMASHX_GNS * 4, hipMemcpyHostToDevice, p->stream));
     const SxHmFields F = hyper_slot_fields(p, false);
-    const dim3 b(256), g((p->n + 255) / 256, F.nf), gk((p->n + 255) / 256);
-    HIPCHK(hipEventRecord(H.ev[0], p->stream));
-    if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
-        hipLaunchKernelGGL(sx_k_hyper_map<true>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, nh, p->n);
-    else
-        hipLaunchKernelGGL(sx_k_hyper_map<false>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, nh, p->n);
-    HIPCHK(hipEventRecord(H.ev[1], p->stream));
-    hipLaunchKernelGGL(sx_k_prep_routing, gk, b, 0, p->stream, p->A);
-    p->jr_ready = false;
-    HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventElapsedTime(&H.map_ms, H.ev[0], H.ev[1]));
+    if ((rc = timed_upload(p, H.tm, [&] { hyper_map(p, F); }))) return rc;
     p->uploaded = true;
     H.mapped = true;
     return 0;
@@ -3128,34 +3122,29 @@ int smashx_hyper_gradient(smashx_plan* p, float* hyper_parameters_b, float* hype
     if (!H.mapped || !p->uploaded) return fail(SMASHX_E_STATE, "smashx_hyper_gradient: no smashx_hyper_upload with the descriptors the plan holds");
     if (!(p->adj_ready && p->last_adjoint)) return fail(SMASHX_E_STATE, "smashx_hyper_gradient: the last sweep was not an adjoint sweep");
     if ((rc = set_device(p))) return rc;
-    const int nh = H.nh;
+    const int nh = H.nh, nd = H.dsc.nd;
     const SxHmFields F = hyper_slot_fields(p, true);
     const int nchain = F.nf * nh;
     // cells per span: from the environment, else what keeps the staging rows at SX_HM_STAGE_BYTES
-    int span = ens_env("SMASHX_HYPER_SPAN");
+    int span = env_int("SMASHX_HYPER_SPAN");
     if (span <= 0) span = (int)std::max<size_t>(1024, SX_HM_STAGE_BYTES / ((size_t)nchain * 4));
     span = std::min(span, std::max(p->n, 1));
-    if ((rc = ens_grow(p, &H.d_terms, &H.terms_cap, (size_t)span * nchain))) return rc;
-    if ((rc = ens_grow(p, &H.d_sums, &H.sums_cap, (size_t)nchain))) return rc;
-    if ((rc = hyper_events(p))) return rc;
+    if ((rc = dev_grow(p, &H.d_terms, &H.terms_cap, (size_t)span * nchain))) return rc;
+    if ((rc = dev_grow(p, &H.d_sums, &H.sums_cap, (size_t)nchain)) || (rc = map_events(H.tm))) return rc;
     H.nchain = nchain; H.span = span;
-    HIPCHK(hipEventRecord(H.ev[2], p->stream));
-    HIPCHK(hipMemsetAsync(H.d_sums, 0, (size_t)nchain * 4, p->stream));
-    for (int c0 = 0; c0 < p->n; c0 += span) {
-        const int ns = std::min(span, p->n - c0);
-        const dim3 b(256), g((ns + 255) / 256, F.nf);
-        if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
-            hipLaunchKernelGGL(sx_k_hyper_terms<true>, g, b, 0, p->stream, F, H.d_h, H.d_desc, H.d_order, H.nd, nh, p->n, c0, ns, H.d_terms, nchain);
-        else
-            hipLaunchKernelGGL(sx_k_hyper_terms<false>, g, b, 0, p->stream, F, H.d_h, H.d_desc, H.d_order, H.nd, nh, p->n, c0, ns, H.d_terms, nchain);
-        hipLaunchKernelGGL(sx_k_hyper_walk, dim3((nchain + 63) / 64), dim3(64), 0, p->stream, H.d_terms, ns, nchain, H.d_sums, c0 > 0 ? 1 : 0);
-    }
-    HIPCHK(hipEventRecord(H.ev[3], p->stream));
     std::vector<float> sums((size_t)nchain);
-    HIPCHK(hipMemcpyAsync(sums.data(), H.d_sums, (size_t)nchain * 4, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventElapsedTime(&H.grad_ms, H.ev[2], H.ev[3]));
+    rc = timed_gradient(p, H.tm, H.d_sums, sums, [&] {
+        for (int c0 = 0; c0 < p->n; c0 += span) {
+            const int ns = std::min(span, p->n - c0);
+            const dim3 b(256), g((ns + 255) / 256, F.nf);
+            if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
+                hipLaunchKernelGGL(sx_k_hyper_terms<true>, g, b, 0, p->stream, F, H.d_h, H.dsc.d_desc, H.dsc.d_order, nd, nh, p->n, c0, ns, H.d_terms, nchain);
+            else
+                hipLaunchKernelGGL(sx_k_hyper_terms<false>, g, b, 0, p->stream, F, H.d_h, H.dsc.d_desc, H.dsc.d_order, nd, nh, p->n, c0, ns, H.d_terms, nchain);
+            hipLaunchKernelGGL(sx_k_hyper_walk, dim3((nchain + 63) / 64), dim3(64), 0, p->stream, H.d_terms, ns, nchain, H.d_sums, c0 > 0 ? 1 : 0);
+        }
+    });
+    if (rc) return rc;
     sx_hh_close(sums.data(), F.field, F.nf, nh, hyper_parameters_b, hyper_states_b);
     return 0;
 }
@@ -3176,15 +3165,9 @@ int smashx_hyper_fields(smashx_plan* p, smashx_parameters* params, smashx_states
         if (s < 0) {
             SxHmFields F{};
             F.nf = 1; F.field[0] = f; F.lb[0] = field_lb(p, f); F.w[0] = field_ub(p, f) - field_lb(p, f); F.val[0] = H.d_tmp;
-            const dim3 b(256), g((p->n + 255) / 256, 1);
-            if (H.mapping == SMASHX_HYPER_POLYNOMIAL)
-                hipLaunchKernelGGL(sx_k_hyper_map<true>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, H.nh, p->n);
-            else
-                hipLaunchKernelGGL(sx_k_hyper_map<false>, g, b, 0, p->stream, F, H.d_h, H.d_desc, p->d_cell_flat, H.nd, H.nh, p->n);
+            hyper_map(p, F);
         }
-        HIPCHK(hipMemcpyAsync(cellv.data(), src, (size_t)p->n * 4, hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(hipStreamSynchronize(p->stream));
-        sx_hh_scatter(cellv.data(), p->sch.cell_flat, h);
+        if ((rc = read_back(p, src, cellv, h))) return rc;
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -3193,30 +3176,20 @@ int smashx_hyper_fields(smashx_plan* p, smashx_parameters* params, smashx_states
 int smashx_hyper_info(const smashx_plan* p, int info[4], float device_ms[2]) {
     if (!p || !info || !device_ms) return fail(SMASHX_E_ARG, "null argument");
     const smashx_plan::Hyper& H = p->hyp;
-    info[0] = H.nd; info[1] = H.nh; info[2] = H.nchain; info[3] = H.span;
-    device_ms[0] = H.map_ms; device_ms[1] = H.grad_ms;
+    info[0] = H.dsc.nd; info[1] = H.nh; info[2] = H.nchain; info[3] = H.span;
+    device_ms[0] = H.tm.map_ms; device_ms[1] = H.tm.grad_ms;
     return 0;
 }
 
 // ---- the ANN regionalisation on the device (include/smashx_ann.h, sx_annmap.h) and its host twin (sx_annhost.h) ---------------------------
 namespace {
-extern "C++" {
-template <class T> int ann_grow(smashx_plan* p, T** buf, size_t* cap, size_t need) {
-    if (*cap >= need) return 0;
-    if (*buf) p->dfree(*buf);
-    *buf = nullptr; *cap = 0;
-    int rc = p->dmalloc(buf, need); if (rc) return rc;
-    *cap = need;
-    return 0;
-}
-}
 // what smashx_ann_upload / _gradient / _fields refuse before they look at their own state, in the order of the header's table
 int ann_refusal(const smashx_plan* p, const char* who) {
     if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, std::string(who) + ": a tiled plan (the weight gradient is a whole-grid sum)");
     const smashx_plan::Ann& A = p->ann;
-    if (!A.have_desc) return fail(SMASHX_E_STATE, std::string(who) + ": no descriptors set (smashx_ann_set_descriptors)");
+    if (!A.dsc.have) return fail(SMASHX_E_STATE, std::string(who) + ": no descriptors set (smashx_ann_set_descriptors)");
     if (!A.have_net) return fail(SMASHX_E_STATE, std::string(who) + ": no net set (smashx_ann_set_net)");
-    if (A.nd != A.net.nd) return fail(SMASHX_E_STATE, std::string(who) + ": the net's input width is not the number of descriptors");
+    if (A.dsc.nd != A.net.nd) return fail(SMASHX_E_STATE, std::string(who) + ": the net's input width is not the number of descriptors");
     if (!p->uploaded) return fail(SMASHX_E_STATE, std::string(who) + ": no smashx_upload of the background fields");
     // compute_jreg reads the planes smashx_upload placed beside the background, not the mapped ones, and its gradient is added at
     // download, behind the cell gradients the adjoint map reads
@@ -3232,13 +3205,8 @@ SxHmFields ann_fields_of(smashx_plan* p, bool grad) {
     for (int e = 0; e < F.nf; ++e) {
         const int f = A.field[e], s = sx_field_slot(p->st, f);
         F.field[e] = f;
-        if (s >= 0) {
-            const SlotVecs V = slot_vecs(p, s);
-            F.val[e] = V.val; F.start[e] = V.start != V.val ? V.start : nullptr; F.full[e] = p->d_full[f];
-            F.grad[e] = grad ? V.grad : nullptr;
-        } else {
-            F.val[e] = A.d_extra + (size_t)extra++ * std::max(p->n, 1);
-        }
+        if (s >= 0) slot_entry(p, F, e, f, s, grad);
+        else F.val[e] = A.d_extra + (size_t)extra++ * std::max(p->n, 1);
     }
     return F;
 }
@@ -3246,10 +3214,6 @@ int ann_extra_count(const smashx_plan* p) {
     int extra = 0;
     for (int e = 0; e < p->ann.net.ncv; ++e) if (sx_field_slot(p->st, p->ann.field[e]) < 0) ++extra;
     return extra;
-}
-int ann_events(smashx_plan* p) {
-    for (hipEvent_t& e : p->ann.ev) if (!e) HIPCHK(hipEventCreate(&e));
-    return 0;
 }
 // the LDS of a workgroup of the map / terms kernels; above 64 KiB a kernel has to be told
 int ann_lds(const smashx_plan* p, size_t* lds) {
@@ -3271,20 +3235,10 @@ int smashx_ann_set_descriptors(smashx_plan* p, int nd, const float* descriptor) 
     if (!p || !descriptor) return fail(SMASHX_E_ARG, "smashx_ann_set_descriptors: null argument");
     if (nd < 1) return fail(SMASHX_E_ARG, "smashx_ann_set_descriptors: nd < 1");
     if (p->tiled) return fail(SMASHX_E_UNSUPPORTED, "smashx_ann_set_descriptors: a tiled plan (the weight gradient is a whole-grid sum)");
-    smashx_plan::Ann& A = p->ann;
     int rc = set_device(p); if (rc) return rc;
-    std::vector<float> g;
-    sx_hh_gather(descriptor, nd, (size_t)p->n2, p->sch.cell_flat, g);
-    if (!A.d_order && (rc = p->upload_vec(&A.d_order, sx_hh_order(p->sch.cell_flat)))) return rc;
-    const bool same = A.have_desc && A.nd == nd && g.size() == A.h_desc.size() &&
-                      std::memcmp(g.data(), A.h_desc.data(), g.size() * 4) == 0;      // (bits: a NaN equals itself here)
-    if (!same) {
-        if ((rc = ann_grow(p, &A.d_desc, &A.desc_cap, std::max<size_t>(g.size(), 1)))) return rc;
-        if (!g.empty()) HIPCHK(hipMemcpy(A.d_desc, g.data(), g.size() * 4, hipMemcpyHostToDevice));
-        A.h_desc.swap(g);
-        A.mapped = false;
-    }
-    A.nd = nd; A.have_desc = true;
+    bool changed = false;
+    if ((rc = set_descriptors(p, p->ann.dsc, nd, descriptor, &changed))) return rc;
+    if (changed) p->ann.mapped = false;
     return 0;
 }
 
@@ -3302,8 +3256,8 @@ int smashx_ann_set_net(smashx_plan* p, int nlayers, const int* kind, const int* 
     // graph is still built first, with a stand-in width of 1, only so that a graph that is none ranks ahead of that (SMASHX_E_ARG)
     smashx_plan::Ann& A = p->ann;
     SxAnnNet N{};
-    int rc = ann_host_net(A.have_desc ? A.nd : 1, nlayers, kind, width, ncv, lower, upper, &N); if (rc) return rc;
-    if (!A.have_desc) return fail(SMASHX_E_STATE, "smashx_ann_set_net: no descriptors set (their number is the net's input width)");
+    int rc = ann_host_net(A.dsc.have ? A.dsc.nd : 1, nlayers, kind, width, ncv, lower, upper, &N); if (rc) return rc;
+    if (!A.dsc.have) return fail(SMASHX_E_STATE, "smashx_ann_set_net: no descriptors set (their number is the net's input width)");
     if (const char* why = sx_annh_device_refusal(N)) return fail(SMASHX_E_UNSUPPORTED, std::string("smashx_ann_set_net: ") + why);
     A.net = N;
     for (int e = 0; e < ncv; ++e) A.field[e] = field[e];
@@ -3317,20 +3271,16 @@ int smashx_ann_upload(smashx_plan* p, const double* weights) {
     if ((rc = set_device(p))) return rc;
     smashx_plan::Ann& A = p->ann;
     size_t lds = 0;
-    if ((rc = ann_grow(p, &A.d_w, &A.w_cap, (size_t)A.net.nw))) return rc;
-    if ((rc = ann_grow(p, &A.d_extra, &A.extra_cap, (size_t)std::max(ann_extra_count(p), 1) * std::max(p->n, 1)))) return rc;
-    if ((rc = ann_events(p)) || (rc = ann_lds(p, &lds))) return rc;
+    if ((rc = dev_grow(p, &A.d_w, &A.w_cap, (size_t)A.net.nw))) return rc;
+    if ((rc = dev_grow(p, &A.d_extra, &A.extra_cap, (size_t)std::max(ann_extra_count(p), 1) * std::max(p->n, 1)))) return rc;
+    if ((rc = map_events(A.tm)) || (rc = ann_lds(p, &lds))) return rc;
     HIPCHK(hipMemcpyAsync(A.d_w, weights, (size_t)A.net.nw * 8, hipMemcpyHostToDevice, p->stream));
     const SxHmFields F = ann_fields_of(p, false);
-    const dim3 b(SX_ANN_BLOCK), g((p->n + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK), gk((p->n + 255) / 256);
-    HIPCHK(hipEventRecord(A.ev[0], p->stream));
-    if (p->n > 0) hipLaunchKernelGGL(sx_k_ann_map, g, b, lds, p->stream, A.net, F, A.d_w, A.d_desc, p->d_cell_flat, p->n);
-    HIPCHK(hipEventRecord(A.ev[1], p->stream));
-    hipLaunchKernelGGL(sx_k_prep_routing, gk, dim3(256), 0, p->stream, p->A);
-    p->jr_ready = false;
-    HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventElapsedTime(&A.map_ms, A.ev[0], A.ev[1]));
+    const dim3 b(SX_ANN_BLOCK), g((p->n + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK);
+    rc = timed_upload(p, A.tm, [&] {
+        if (p->n > 0) hipLaunchKernelGGL(sx_k_ann_map, g, b, lds, p->stream, A.net, F, A.d_w, A.dsc.d_desc, p->d_cell_flat, p->n);
+    });
+    if (rc) return rc;
     p->last_adjoint = 0;           // a gradient belongs to a sweep behind THIS upload
     A.mapped = true;
     return 0;
@@ -3345,30 +3295,26 @@ int smashx_ann_gradient(smashx_plan* p, double* weights_b) {
     if ((rc = set_device(p))) return rc;
     const int nw = A.net.nw;
     // cells per span, whole blocks: from the environment, else what keeps the staging rows at SX_ANN_STAGE_BYTES
-    long span = ens_env("SMASHX_ANN_SPAN");
+    long span = env_int("SMASHX_ANN_SPAN");
     if (span <= 0) span = (long)std::max<size_t>(16, SX_ANN_STAGE_BYTES / ((size_t)nw * 8)) * SX_ANN_BLOCK;
     span = (span + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK * SX_ANN_BLOCK;
     span = std::min<long>(span, (std::max(p->n, 1) + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK * SX_ANN_BLOCK);
     size_t lds = 0;
-    if ((rc = ann_grow(p, &A.d_terms, &A.terms_cap, (size_t)(span / SX_ANN_BLOCK) * nw))) return rc;
-    if ((rc = ann_grow(p, &A.d_sums, &A.sums_cap, (size_t)nw))) return rc;
-    if ((rc = ann_events(p)) || (rc = ann_lds(p, &lds))) return rc;
+    if ((rc = dev_grow(p, &A.d_terms, &A.terms_cap, (size_t)(span / SX_ANN_BLOCK) * nw))) return rc;
+    if ((rc = dev_grow(p, &A.d_sums, &A.sums_cap, (size_t)nw))) return rc;
+    if ((rc = map_events(A.tm)) || (rc = ann_lds(p, &lds))) return rc;
     A.span = (int)span;
     const SxHmFields F = ann_fields_of(p, true);
-    HIPCHK(hipEventRecord(A.ev[2], p->stream));
-    HIPCHK(hipMemsetAsync(A.d_sums, 0, (size_t)nw * 8, p->stream));
-    for (long c0 = 0; c0 < p->n; c0 += span) {
-        const int ns = (int)std::min<long>(span, p->n - c0);
-        const int nb = (ns + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK;
-        hipLaunchKernelGGL(sx_k_ann_terms, dim3(nb), dim3(SX_ANN_BLOCK), lds, p->stream, A.net, F, A.d_w, A.d_desc, A.d_order, p->n, (int)c0, ns, A.d_terms);
-        hipLaunchKernelGGL(sx_k_ann_walk, dim3((nw + 63) / 64), dim3(64), 0, p->stream, A.d_terms, nb, nw, A.d_sums);
-    }
-    HIPCHK(hipEventRecord(A.ev[3], p->stream));
     std::vector<double> sums((size_t)nw);
-    HIPCHK(hipMemcpyAsync(sums.data(), A.d_sums, (size_t)nw * 8, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventElapsedTime(&A.grad_ms, A.ev[2], A.ev[3]));
+    rc = timed_gradient(p, A.tm, A.d_sums, sums, [&] {
+        for (long c0 = 0; c0 < p->n; c0 += span) {
+            const int ns = (int)std::min<long>(span, p->n - c0);
+            const int nb = (ns + SX_ANN_BLOCK - 1) / SX_ANN_BLOCK;
+            hipLaunchKernelGGL(sx_k_ann_terms, dim3(nb), dim3(SX_ANN_BLOCK), lds, p->stream, A.net, F, A.d_w, A.dsc.d_desc, A.dsc.d_order, p->n, (int)c0, ns, A.d_terms);
+            hipLaunchKernelGGL(sx_k_ann_walk, dim3((nw + 63) / 64), dim3(64), 0, p->stream, A.d_terms, nb, nw, A.d_sums);
+        }
+    });
+    if (rc) return rc;
     std::memcpy(weights_b, sums.data(), (size_t)nw * 8);
     return 0;
 }
@@ -3384,10 +3330,8 @@ int smashx_ann_fields(smashx_plan* p, smashx_parameters* params, smashx_states* 
     for (int e = 0; e < F.nf; ++e) {
         float* const h = host_plane(params, states, F.field[e]);
         if (!h) continue;
-        const float* src = F.start[e] ? F.start[e] : F.val[e];         // what the upload stored: a state's starting values
-        HIPCHK(hipMemcpyAsync(cellv.data(), src, (size_t)p->n * 4, hipMemcpyDeviceToHost, p->stream));
-        HIPCHK(hipStreamSynchronize(p->stream));
-        sx_hh_scatter(cellv.data(), p->sch.cell_flat, h);
+        // what the upload stored: a state's starting values
+        if ((rc = read_back(p, F.start[e] ? F.start[e] : F.val[e], cellv, h))) return rc;
     }
     return 0;
 }
@@ -3395,8 +3339,8 @@ int smashx_ann_fields(smashx_plan* p, smashx_parameters* params, smashx_states* 
 int smashx_ann_info(const smashx_plan* p, int info[4], float device_ms[2]) {
     if (!p || !info || !device_ms) return fail(SMASHX_E_ARG, "null argument");
     const smashx_plan::Ann& A = p->ann;
-    info[0] = A.nd; info[1] = A.have_net ? A.net.nw : 0; info[2] = A.span; info[3] = A.have_net ? A.net.nslots * SX_ANN_BLOCK * 8 : 0;
-    device_ms[0] = A.map_ms; device_ms[1] = A.grad_ms;
+    info[0] = A.dsc.nd; info[1] = A.have_net ? A.net.nw : 0; info[2] = A.span; info[3] = A.have_net ? A.net.nslots * SX_ANN_BLOCK * 8 : 0;
+    device_ms[0] = A.tm.map_ms; device_ms[1] = A.tm.grad_ms;
     return 0;
 }
 

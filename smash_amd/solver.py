@@ -520,16 +520,19 @@ class Solver:
         _lib.check(_lib.lib().smashx_hyper_gradient(self._h, _ptr(hpb), _ptr(hsb)))
         return hpb, hsb
 
+    def _mapped_fields(self, who, call, parameters, states):
+        """hyper_fields / ann_fields: the planes of parameters / states, every one a writeable (nrow, ncol) array, handed to call"""
+        P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
+        S, k2 = _pack(states, STATE_NAMES, _lib.States)
+        for a in k1 + k2:
+            if a.shape != (self.nrow, self.ncol) or not a.flags.writeable:
+                raise _lib.SmashxError(_lib.E_ARG, f"{who}: every plane must be a writeable ({self.nrow}, {self.ncol}) array")
+        _lib.check(call(self._h, C.byref(P), C.byref(S)))
+
     def hyper_fields(self, parameters=None, states=None):
         """The mapped fields of the last hyper_upload into the planes of parameters / states (either may be None): active cells are
         written, the others keep their values."""
-        P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
-        S, k2 = _pack(states, STATE_NAMES, _lib.States)
-        for keep in (k1, k2):
-            for a in keep:
-                if a.shape != (self.nrow, self.ncol) or not a.flags.writeable:
-                    raise _lib.SmashxError(_lib.E_ARG, f"hyper_fields: every plane must be a writeable ({self.nrow}, {self.ncol}) array")
-        _lib.check(_lib.lib().smashx_hyper_fields(self._h, C.byref(P), C.byref(S)))
+        self._mapped_fields("hyper_fields", _lib.lib().smashx_hyper_fields, parameters, states)
 
     def hyper_info(self):
         """{nd, nhyper, chains, span, map_ms, gradient_ms} of the last hyper_upload / hyper_gradient on this plan (smashx_hyper_info)."""
@@ -572,13 +575,7 @@ class Solver:
     def ann_fields(self, parameters=None, states=None):
         """The mapped control fields of the last ann_upload into the planes of parameters / states (either may be None): their active
         cells are written, everything else stays."""
-        P, k1 = _pack(parameters, PARAM_NAMES, _lib.Parameters)
-        S, k2 = _pack(states, STATE_NAMES, _lib.States)
-        for keep in (k1, k2):
-            for a in keep:
-                if a.shape != (self.nrow, self.ncol) or not a.flags.writeable:
-                    raise _lib.SmashxError(_lib.E_ARG, f"ann_fields: every plane must be a writeable ({self.nrow}, {self.ncol}) array")
-        _lib.check(_lib.lib().smashx_ann_fields(self._h, C.byref(P), C.byref(S)))
+        self._mapped_fields("ann_fields", _lib.lib().smashx_ann_fields, parameters, states)
 
     def ann_info(self):
         """{nd, nweights, span, lds_bytes, map_ms, gradient_ms} of the last ann_upload / ann_gradient on this plan (smashx_ann_info)."""

@@ -71,6 +71,26 @@ def test_equals_the_loop_partial_sampling(names):
         assert _same(_resident(ctx, names, sample[:, :S]), lc[:S])
 
 
+def test_a_second_batch_equals_the_ensemble_bit_for_bit():
+    """16384 + 3 samples: one more than a batch holds, so that both routes stage, launch and copy out a second, short batch.  The
+    loop of single runs is not run at this count: include/smashx_sbs.h states res_cost to be smashx_multiple_run's, bit for bit."""
+    import smash_amd
+    g = gu.load("gr_a_12x12x48_nse")
+    names = ("cp", "lr")
+    S = 16384 + 3
+    sample = mu.draw(names, S)
+    ctx = _types(g)
+    setup, mesh, inp, par, sta, out = ctx
+    ec = np.zeros(S, np.float32)
+    smash_amd.compute_multiple_run(setup, mesh, inp, par, sta, out, sample, mu.index_of(names), ec, np.zeros(0, np.float32))
+    ens = inp._smashx_solver.multiple_run_info()
+    rc = _resident(ctx, names, sample)
+    print(f"S={S}: ensemble {ens}, resident {inp._smashx_solver.uniform_costs_info()}, "
+          f"costs differing {int(np.count_nonzero(rc.view(np.uint32) != ec.view(np.uint32)))}")
+    assert ens["n_batches"] == 2, ens
+    assert rc.shape == (S,) and np.all(np.isfinite(ec)) and _same(rc, ec)
+
+
 # ---- hand-made meshes --------------------------------------------------------------------------------------------------------------------
 def _hand(flwdir, gauges, nt, structure="gr-b", dx=1000.0):
     """a case on a hand-made D8 plane: cells with a code in 0..8 are active (0: an outlet that points nowhere), -99 elsewhere"""
@@ -309,4 +329,4 @@ def test_exact_build_runs_this_file():
                         "--deselect", os.path.relpath(os.path.abspath(__file__), ROOT) + "::test_exact_build_runs_this_file"], env=env,
                        capture_output=True, text=True, timeout=1500, cwd=ROOT)
     sys.stdout.write(r.stdout[-8000:])
-    assert r.returncode == 0 and "43 passed" in r.stdout and "skipped" not in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
+    assert r.returncode == 0 and "44 passed" in r.stdout and "skipped" not in r.stdout, r.stdout[-4000:] + r.stderr[-2000:]
