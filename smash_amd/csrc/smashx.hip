@@ -555,17 +555,13 @@ template <class T> int dev_grow(smashx_plan* p, T** buf, size_t* cap, size_t nee
 int env_int(const char* name) { const char* e = getenv(name); return e ? std::max(0, atoi(e)) : 0; }      // a length from the environment; 0: none
 
 // ---- fields (sx_fields.h) on this plan ------------------------------------------------------------------------------------------
-static_assert(SX_NPSLOTS == SX_ENS_NP && SX_NSSLOTS == SX_ENS_NS, "the ensemble kernels number the slots like sx_fields.h");
 // The cell vectors of a slot: its values, the values a sweep starts from (the uploaded states; a parameter's are its values) and its
 // gradient, which doubles as the tangent.  References, resolved at use: the gradient vectors are allocated on the first adjoint sweep.
 struct SlotVecs { float*& val; float*& start; float*& grad; };
 SlotVecs slot_vecs(smashx_plan* p, int slot) {
     SxDeviceArrays& A = p->A;
-    float** const val[SX_NSLOTS] = {&A.ci, &A.cp, &A.cft, &A.cst, &A.exc, &A.lr, &A.px[0], &A.px[1], &A.px[2],
-                                    &A.hi, &A.hp, &A.hft, &A.hst, &A.hlr};
-    float** const grad[SX_NSLOTS] = {&A.ci_b, &A.cp_b, &A.cft_b, &A.cst_b, &A.exc_b, &A.lr_b, &A.px_b[0], &A.px_b[1], &A.px_b[2],
-                                     &A.hi_b, &A.hp_b, &A.hft_b, &A.hst_b, &A.hlr_b};
-    return {*val[slot], sx_slot_is_state(slot) ? p->st0[slot - SX_NPSLOTS] : *val[slot], *grad[slot]};
+    float*& val = sx_slot_vec(A, slot, false);
+    return {val, sx_slot_is_state(slot) ? p->st0[slot - SX_NPSLOTS] : val, sx_slot_vec(A, slot, true)};
 }
 hipStream_t slot_stream(const smashx_plan* p, int slot) { return sx_slot_on_routing(slot) ? p->stream_r : p->stream; }
 // what the options and the caller's structures hold for field idx (0..23)
@@ -2713,7 +2709,7 @@ int ens_tables(smashx_plan* p) {
     int rc;
     if ((rc = p->upload_vec(&E.d_up, up)) || (rc = p->upload_vec(&E.d_upn, upn)) || (rc = p->upload_vec(&E.d_order, order))) return rc;
     if ((rc = p->upload_vec(&E.d_gauge_k, p->sch.gauge_k.empty() ? std::vector<int>(1, 0) : p->sch.gauge_k))) return rc;
-    if ((rc = p->dmalloc(&E.base, (size_t)(SX_ENS_NP + SX_ENS_NS) * p->npad))) return rc;
+    if ((rc = p->dmalloc(&E.base, (size_t)SX_NSLOTS * p->npad))) return rc;
     if ((rc = p->dmalloc(&E.plane, (size_t)p->n2))) return rc;
     HIPCHK(hipEventCreate(&E.ev_a)); HIPCHK(hipEventCreate(&E.ev_b));
     E.nlevels = nlev; E.level_begin = begin; E.tables = true;
@@ -2721,7 +2717,6 @@ int ens_tables(smashx_plan* p) {
     return 0;
 }
 
-static_assert(SX_ENS_NP + SX_ENS_NS == SX_NSLOTS, "the ensemble's slots are the slots of sx_fields.h");
 // The frame of the two sample paths (smashx_multiple_run, smashx_uniform_costs; host side: sx_samplehost.h).  open: the checks and
 // refusals both share, the forest; base: the base fields; arrays: the buffers both need and SxEnsArrays; per batch begin (ev_a, the
 // sample up), the path's own launches, costs, end (ev_b, the path's own copies, one synchronisation, the costs into dst).
@@ -2833,23 +2828,19 @@ int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const s
     const int nchunk = (nt + Tc - 1) / Tc;
     const size_t sSP = (size_t)SP;
     if ((rc = B.arrays(SP, Tc, &X.device_ms))) return rc;
-    if ((rc = dev_grow(p, &X.state, &X.cap_state, (size_t)SX_ENS_NS * n * sSP)) || (rc = dev_grow(p, &X.qt, &X.cap_qt, (size_t)n * Tc * sSP))) return rc;
+    if ((rc = dev_grow(p, &X.state, &X.cap_state, (size_t)SX_NSSLOTS * n * sSP)) || (rc = dev_grow(p, &X.qt, &X.cap_qt, (size_t)n * Tc * sSP))) return rc;
     if (res_qsim && ng > 0 && (rc = dev_grow(p, &X.qout, &X.cap_qout, (size_t)ng * nt * sSP))) return rc;
     SxEnsArrays& E = B.E;
     E.state = X.state; E.qt = X.qt; E.qout = X.qout;
     const dim3 b64(64), bV(64, SX_ENS_CELLS), gV(SP / 64, (n + SX_ENS_CELLS - 1) / SX_ENS_CELLS);
+    static void (*const vert[5])(SxDeviceArrays, SxEnsArrays, int, int) = {sx_k_ens_vert_fwd<1>, sx_k_ens_vert_fwd<2>, sx_k_ens_vert_fwd<3>,
+                                                                           sx_k_ens_vert_fwd<4>, sx_k_ens_vert_fwd<5>};
     for (int bi = 0; bi < B.nbatch; ++bi) {
         if ((rc = B.begin(bi))) return rc;
         hipLaunchKernelGGL(sx_k_ens_init_states, dim3(SP / 64, std::min(n, 65535)), b64, 0, sV, E, B.used_states);
         for (int c = 0; c < nchunk; ++c) {
             const int t0 = c * Tc, T = std::min(Tc, nt - t0);
-            switch (st) {
-                case 1: hipLaunchKernelGGL((sx_k_ens_vert_fwd<1>), gV, bV, 0, sV, p->A, E, t0, T); break;
-                case 2: hipLaunchKernelGGL((sx_k_ens_vert_fwd<2>), gV, bV, 0, sV, p->A, E, t0, T); break;
-                case 3: hipLaunchKernelGGL((sx_k_ens_vert_fwd<3>), gV, bV, 0, sV, p->A, E, t0, T); break;
-                case 4: hipLaunchKernelGGL((sx_k_ens_vert_fwd<4>), gV, bV, 0, sV, p->A, E, t0, T); break;
-                default: hipLaunchKernelGGL(sx_k_ens_vert_fwd_vic, gV, bV, 0, sV, p->A, E, t0, T); break;
-            }
+            hipLaunchKernelGGL(vert[st - 1], gV, bV, 0, sV, p->A, E, t0, T);
             // one launch per level of the forest: stream order is the dependency
             for (int l = 0; l < X.nlevels; ++l) {
                 const int i0 = X.level_begin[l], m = X.level_begin[l + 1] - i0;
@@ -2938,16 +2929,6 @@ int res_tables(smashx_plan* p) {
     return 0;
 }
 
-extern "C++" {
-template <int ST>
-int res_launch(smashx_plan* p, const SxEnsArrays& E, const SxResTables& R, int SP, hipStream_t sV) {
-    auto& X = p->ens;
-    if (X.res_lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sx_k_res_fwd<ST>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X.res_lds));
-    hipLaunchKernelGGL((sx_k_res_fwd<ST>), dim3(SP), dim3(X.res_block), X.res_lds, sV, p->A, E, R, p->nt);
-    return 0;
-}
-}  // extern "C++"
 }  // namespace
 
 int smashx_uniform_costs(smashx_plan* p, const smashx_parameters* params, const smashx_states* states, int nfields,
@@ -2964,18 +2945,16 @@ int smashx_uniform_costs(smashx_plan* p, const smashx_parameters* params, const 
     SxResTables R{};
     R.nlevels = X.nlevels; R.cell = X.r_cell; R.level = X.r_level; R.upline = X.r_upline; R.upn = X.r_upn; R.ownline = X.r_ownline;
     R.gfirst = X.r_gfirst; R.gnext = X.r_gnext;
+    static void (*const kernel[5])(SxDeviceArrays, SxEnsArrays, SxResTables, int) = {sx_k_res_fwd<1>, sx_k_res_fwd<2>, sx_k_res_fwd<3>,
+                                                                                       sx_k_res_fwd<4>, sx_k_res_fwd<5>};
+    const auto res = kernel[p->st - 1];
     std::vector<float> out(nsamples);
     for (int bi = 0; bi < B.nbatch; ++bi) {
         if ((rc = B.begin(bi))) return rc;
         if (p->ng > 0) {    // without a gauge the cost is 0 and nothing has to run
-            switch (p->st) {
-                case 1: rc = res_launch<1>(p, B.E, R, B.cnt, p->stream); break;
-                case 2: rc = res_launch<2>(p, B.E, R, B.cnt, p->stream); break;
-                case 3: rc = res_launch<3>(p, B.E, R, B.cnt, p->stream); break;
-                case 4: rc = res_launch<4>(p, B.E, R, B.cnt, p->stream); break;
-                default: rc = res_launch<5>(p, B.E, R, B.cnt, p->stream); break;
-            }
-            if (rc) return rc;
+            if (X.res_lds > 48 * 1024)
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(res), hipFuncAttributeMaxDynamicSharedMemorySize, (int)X.res_lds));
+            hipLaunchKernelGGL(res, dim3(B.cnt), dim3(X.res_block), X.res_lds, p->stream, p->A, B.E, R, p->nt);
         }
         if ((rc = B.costs()) || (rc = B.end(out.data()))) return rc;
     }

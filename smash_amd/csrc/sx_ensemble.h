@@ -11,26 +11,25 @@
 // The forcing of a cell-step is ONE value per wavefront (a broadcast load from the plan's resident rows, whatever their layout), and
 // the wave-uniform still-step shortcut of sx_ops.h fires on the forcing alone.
 //
-// The arithmetic is that of the single run, by construction: the vertical step IS sx_vertical_step<ST> / sx_vic_step, the routing
-// statement restates sx_route_fwd_group (sx_kernels.h:854-900, TMODE 0) with the per-cell invariants of sx_k_prep_routing
-// (sx_kernels.h:318-328) -- restated, not shared, because the group kernel works on float4 time blocks behind its LDS exchange and
-// a function carved out of its body would change its schedule -- and the cost folds the gauge series through sx_sums_add /
-// sx_gauge_jobs of sx_cost.h, the functions sx_k_cost_sums / sx_k_cost_final call.  sx_div4 is four sx_div (sx_math.h), so the
-// scalar quotients below are the same bits.
+// The arithmetic is that of the single run, by construction: the cell is set up by the functions the single run's kernels call
+// (sx_cell_params, sx_fwd_powers, sx_levels_in / _out, sx_vic_params: sx_ops.h, sx_vic.h) from another field source, the vertical
+// step IS sx_vertical_step<ST> / sx_vic_step, the routing is sx_route_cell / sx_route_step (sx_ops.h), whose invariants
+// sx_k_prep_routing stores for the group kernels, and the cost folds the gauge series through sx_sums_add / sx_gauge_jobs of
+// sx_cost.h, the functions sx_k_cost_sums / sx_k_cost_final call.  One statement is still restated: sx_route_step says in scalars
+// what sx_route_fwd_group (sx_kernels.h, TMODE 0) says on float4 time blocks behind its LDS exchange, because a function carved
+// out of the group kernel's body would change its schedule.
 #pragma once
 
 #include "sx_cost.h"
 #include "sx_kernels.h"
 
-#define SX_ENS_NP 9          // parameter slots (smashx.hip param_field)
-#define SX_ENS_NS 5          // state slots
 #define SX_ENS_CELLS 4       // cells (= wavefronts) per vertical workgroup
 
 struct SxEnsArrays {
     int n, npad, SP, Tc;
     const float* base;
     const float* sample;
-    int smap[SX_ENS_NP + SX_ENS_NS];     // row of `sample` that replaces the slot, -1: the base field
+    int smap[SX_NSLOTS];         // row of `sample` that replaces the slot, -1: the base field
     float* state;
     float* qt;
     const int* up;               // [n][8] upstream cells in D8 order 1..8 (md_routing_operator.f90:37-53), the first upn[k] entries
@@ -55,13 +54,13 @@ __global__ __launch_bounds__(64) void sx_k_ens_init_states(SxEnsArrays E, int us
     const int s = blockIdx.x * 64 + threadIdx.x;
     for (int k = blockIdx.y; k < E.n; k += gridDim.y) {
 #pragma unroll
-        for (int i = 0; i < SX_ENS_NS; ++i)
-            if (used_mask >> i & 1) E.state[((size_t)i * E.n + k) * E.SP + s] = sx_ens_val(E, SX_ENS_NP + i, k, s);
+        for (int i = 0; i < SX_NSSLOTS; ++i)
+            if (used_mask >> i & 1) E.state[((size_t)i * E.n + k) * E.SP + s] = sx_ens_val(E, SX_SLOT_HI + i, k, s);
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// vertical forward: one thread per (cell, sample) marches the time chunk [t0, t0 + T)
+// vertical forward: one thread per (cell, sample) marches the time chunk [t0, t0 + T).  ST = 1..4: gr-a .. gr-d, 5: vic-a
 // ------------------------------------------------------------------------------------------------
 template <int ST>
 __global__ __launch_bounds__(64 * SX_ENS_CELLS) void sx_k_ens_vert_fwd(SxDeviceArrays A, SxEnsArrays E, int t0, int T) {
@@ -70,59 +69,38 @@ __global__ __launch_bounds__(64 * SX_ENS_CELLS) void sx_k_ens_vert_fwd(SxDeviceA
     const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * SX_ENS_CELLS + threadIdx.y));     // one cell per wavefront
     if (k >= E.n) return;
     const size_t SP = (size_t)E.SP, nS = (size_t)E.n * SP;
+    // the ensemble's field source (sx_ops.h).  Captured by value: behind a captured reference to E the select of sx_ens_val stays a
+    // branch per field (40 to 70 instructions more per kernel, two registers more in sx_k_res_fwd)
+    const auto val = [=](int slot) { return sx_ens_val(E, slot, k, s); };
+    float* sv = E.state + (size_t)k * SP + s;                // the running levels are a source and a sink of their own
+    const auto lev = [=](int slot) { return sv[(size_t)(slot - SX_SLOT_HI) * nS]; };
+    const auto lev_out = [=](int slot, float h) { sv[(size_t)(slot - SX_SLOT_HI) * nS] = h; };
 
     SxCellParams P;
-    float hi = 0.f, hp = 0.f, hft = 0.f, hst = 0.f;
-    P.ci = (ST == 2 || ST == 3) ? sx_ens_val(E, 0, k, s) : 1.f;
-    P.cp = sx_ens_val(E, 1, k, s);
-    P.cft = sx_ens_val(E, 2, k, s);
-    P.cst = (ST == 3) ? sx_ens_val(E, 3, k, s) : 1.f;
-    P.exc = (ST != 4) ? sx_ens_val(E, 4, k, s) : 0.f;
-    sx_cell_params_init(P);
-    P.cft_m4 = sx_pow_m4(P.cft);
-    P.cst_m4 = (ST == 3) ? sx_pow_m4(P.cst) : 1.f;
-    float* sv = E.state + (size_t)k * SP + s;
-    if (ST == 2 || ST == 3) hi = sv[0];
-    hp = sv[nS];
-    hft = sv[2 * nS];
-    if (ST == 3) hst = sv[3 * nS];
-
+    SxVicParams V;
+    float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f, cusl2_m4 = 0.f;      // gr: hi, hp, hft, hst; vic-a: husl1, husl2, hlsl
+    if constexpr (ST == 5) {
+        V = sx_vic_params(val);
+        cusl2_m4 = sx_pow_m4(V.cusl2);
+        sx_vic_levels_in(lev, h0, h1, h2);
+    } else {
+        sx_cell_params<ST>(val, P);
+        sx_fwd_powers<ST>(P);
+        sx_levels_in<ST>(lev, h0, h1, h2, h3);
+    }
     const unsigned kb = (unsigned)k * 4u;
     float* q = E.qt + (size_t)k * E.Tc * SP + s;
     for (int tt = 0; tt < T; ++tt) {
         float prcp, pet;
         sx_forcing_at(A, t0 + tt, kb, prcp, pet);            // wave-uniform address: one value per wavefront
-        const bool still = SX_STILL && sx_wave_all(sx_is_still<ST>(prcp, pet, hi, hp));
-        q[(size_t)tt * SP] = sx_vertical_step<ST>(P, prcp, pet, hi, hp, hft, hst, still);
+        if constexpr (ST == 5) q[(size_t)tt * SP] = sx_vic_step(V, cusl2_m4, prcp, pet, h0, h1, h2);
+        else {
+            const bool still = SX_STILL && sx_wave_all(sx_is_still<ST>(prcp, pet, h0, h1));
+            q[(size_t)tt * SP] = sx_vertical_step<ST>(P, prcp, pet, h0, h1, h2, h3, still);
+        }
     }
-    if (ST == 2 || ST == 3) sv[0] = hi;
-    sv[nS] = hp;
-    sv[2 * nS] = hft;
-    if (ST == 3) sv[3 * nS] = hst;
-}
-
-// vic-a twin (slots as in sx_vic_load: b, cusl1, cusl2, clsl, ks -> 0..4, ds, dsm, ws -> 6..8; husl1, husl2, hlsl -> states 0..2)
-__global__ __launch_bounds__(64 * SX_ENS_CELLS) void sx_k_ens_vert_fwd_vic(SxDeviceArrays A, SxEnsArrays E, int t0, int T) {
-    SX_LIBM_INIT();
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    const int k = __builtin_amdgcn_readfirstlane((int)(blockIdx.y * SX_ENS_CELLS + threadIdx.y));
-    if (k >= E.n) return;
-    const size_t SP = (size_t)E.SP, nS = (size_t)E.n * SP;
-    SxVicParams P;
-    P.b = sx_ens_val(E, 0, k, s); P.cusl1 = sx_ens_val(E, 1, k, s); P.cusl2 = sx_ens_val(E, 2, k, s); P.clsl = sx_ens_val(E, 3, k, s);
-    P.ks = sx_ens_val(E, 4, k, s); P.ds = sx_ens_val(E, 6, k, s); P.dsm = sx_ens_val(E, 7, k, s); P.ws = sx_ens_val(E, 8, k, s);
-    sx_vic_derive(P);
-    const float cusl2_m4 = sx_pow_m4(P.cusl2);
-    float* sv = E.state + (size_t)k * SP + s;
-    float husl1 = sv[0], husl2 = sv[nS], hlsl = sv[2 * nS];
-    const unsigned kb = (unsigned)k * 4u;
-    float* q = E.qt + (size_t)k * E.Tc * SP + s;
-    for (int tt = 0; tt < T; ++tt) {
-        float prcp, pet;
-        sx_forcing_at(A, t0 + tt, kb, prcp, pet);
-        q[(size_t)tt * SP] = sx_vic_step(P, cusl2_m4, prcp, pet, husl1, husl2, hlsl);
-    }
-    sv[0] = husl1; sv[nS] = husl2; sv[2 * nS] = hlsl;
+    if constexpr (ST == 5) sx_vic_levels_out(lev_out, h0, h1, h2);
+    else sx_levels_out<ST>(lev_out, h0, h1, h2, h3);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -138,16 +116,8 @@ __global__ __launch_bounds__(64) void sx_k_ens_route_fwd(SxDeviceArrays A, SxEns
     const int s = blockIdx.x * 64 + threadIdx.x;
     const int k = __builtin_amdgcn_readfirstlane(E.order[i0 + (int)blockIdx.y]);
     const size_t SP = (size_t)E.SP, row = (size_t)E.Tc * SP;
-    // per-cell invariants as sx_k_prep_routing forms them; lr may be a sampled field, so rt_a is per lane
-    const float lr = sx_ens_val(E, 5, k, s);
-    const float a = sx_expf(-A.dt / (lr * 60.f));
-    const int facc = A.flwacc[k];
-    const float f = (float)(facc - 1);
-    const float den = 0.001f * A.dx * A.dx * f;
-    const bool hasup = facc > 1;
-    const float dt = A.dt, dx = A.dx;
-    const SxDiv dden = sx_mkdiv(den), ddt = sx_mkdiv(dt);
-    float* hl = E.state + ((size_t)4 * E.n + k) * SP + s;
+    const SxRouteCell R = sx_route_cell(A, sx_ens_val(E, SX_SLOT_LR, k, s), k);      // lr may be a sampled field, so rt_a is per lane
+    float* hl = E.state + ((size_t)(SX_SLOT_HLR - SX_SLOT_HI) * E.n + k) * SP + s;
     float hlr = *hl;
     const int nup = __builtin_amdgcn_readfirstlane(E.upn[k]);
     const int* upk = E.up + (size_t)k * 8;
@@ -170,16 +140,8 @@ __global__ __launch_bounds__(64) void sx_k_ens_route_fwd(SxDeviceArrays A, SxEns
             for (int i = 0; i < SX_ENS_RB; ++i) sum[i] = sum[i] + uc[(size_t)min(tb + i, T - 1) * SP];
         }
 #pragma unroll
-        for (int i = 0; i < SX_ENS_RB; ++i) {
-            if (tb + i < T) {
-                const float qup = hasup ? sx_div(sum[i] * dt, dden) : 0.f;
-                const float hr_imd = hlr + qup;
-                const float hnew = hr_imd * a;
-                const float qro = hr_imd - hnew;
-                hlr = hnew;
-                q[(size_t)(tb + i) * SP] = sx_div((qt[i] + qro * f) * dx * dx * 0.001f, ddt);
-            }
-        }
+        for (int i = 0; i < SX_ENS_RB; ++i)
+            if (tb + i < T) q[(size_t)(tb + i) * SP] = sx_route_step(R, sum[i], qt[i], hlr);
     }
     *hl = hlr;
 }

@@ -11,7 +11,10 @@
 
 constexpr int SX_NFIELDS = SMASHX_GNP + SMASHX_GNS;
 constexpr int SX_NPSLOTS = 9, SX_NSSLOTS = 5, SX_NSLOTS = SX_NPSLOTS + SX_NSSLOTS;
-constexpr int SX_SLOT_LR = 5, SX_SLOT_HLR = 13;
+// the slots by name (the GR names; vic-a's occupants are listed above)
+enum : int { SX_SLOT_CI, SX_SLOT_CP, SX_SLOT_CFT, SX_SLOT_CST, SX_SLOT_EXC, SX_SLOT_LR, SX_SLOT_PX0, SX_SLOT_PX1, SX_SLOT_PX2,
+             SX_SLOT_HI, SX_SLOT_HP, SX_SLOT_HFT, SX_SLOT_HST, SX_SLOT_HLR };
+static_assert(SX_SLOT_PX2 + 1 == SX_NPSLOTS && SX_SLOT_HLR + 1 == SX_NSLOTS, "14 names for 14 slots");
 
 #define SX_F_P(name) SMASHX_P_##name
 #define SX_F_S(name) (SMASHX_GNP + SMASHX_S_##name)

@@ -223,6 +223,34 @@ struct SxDeviceArrays {
     long long* gtime;             // diagnostics (SMASHX_TRACE_GROUPS=1): [2 passes][ngroups][start, end] wall_clock64 ticks, else null
 };
 
+// the per-cell vector of a slot (sx_fields.h): its values, or its gradient, which doubles as the tangent.  Arrays: SxDeviceArrays,
+// const or not -- the host driver takes the pointer by reference (slot_vecs, smashx.hip).
+template <class Arrays>
+__host__ __device__ __forceinline__ auto& sx_slot_vec(Arrays& A, int slot, bool grad) {
+    switch (slot) {
+        case SX_SLOT_CI: return grad ? A.ci_b : A.ci;
+        case SX_SLOT_CP: return grad ? A.cp_b : A.cp;
+        case SX_SLOT_CFT: return grad ? A.cft_b : A.cft;
+        case SX_SLOT_CST: return grad ? A.cst_b : A.cst;
+        case SX_SLOT_EXC: return grad ? A.exc_b : A.exc;
+        case SX_SLOT_LR: return grad ? A.lr_b : A.lr;
+        case SX_SLOT_PX0: case SX_SLOT_PX1: case SX_SLOT_PX2: return grad ? A.px_b[slot - SX_SLOT_PX0] : A.px[slot - SX_SLOT_PX0];
+        case SX_SLOT_HI: return grad ? A.hi_b : A.hi;
+        case SX_SLOT_HP: return grad ? A.hp_b : A.hp;
+        case SX_SLOT_HFT: return grad ? A.hft_b : A.hft;
+        case SX_SLOT_HST: return grad ? A.hst_b : A.hst;
+        default: return grad ? A.hlr_b : A.hlr;
+    }
+}
+// The plan's field source and sink (sx_ops.h) for cell k.  The slot is a literal at every call, so the switch folds at compile time.
+template <bool GRAD = false>
+struct SxPlanCell {
+    const SxDeviceArrays& A;
+    int k;
+    __device__ __forceinline__ float operator()(int slot) const { return sx_slot_vec(A, slot, GRAD)[k]; }
+    __device__ __forceinline__ void operator()(int slot, float v) const { sx_slot_vec(A, slot, GRAD)[k] = v; }
+};
+
 // ------------------------------------------------------------------------------------------------
 // Staging rows of the chained groups.  The groups of the rounds >= 1 are the river's main stems: a few workgroups whose super-step
 // is a latency chain, and every memory instruction in it whose 64 lanes touch 64 different lines (slots of one wave sit at different
@@ -429,14 +457,23 @@ struct SxForcing {
     }
 };
 
-// both values of step t at once, layout decided at run time (kernels off the headline path: no prefetch)
-__device__ __forceinline__ void sx_forcing_at(const SxDeviceArrays& A, int t, unsigned kb, float& p, float& e) {
+// both values of step t at once, layout decided at run time (kernels off the headline path: no prefetch).  How a cell's word of a
+// row is loaded is the caller's choice.  ROW: the row is wave-uniform (every lane is at the same step), so it goes through a buffer
+// descriptor with the cell's byte offset c = 4 x cell, and the hour's ratio through the scalar unit.  Otherwise: per-lane addresses
+// of cell c, for lanes that are at different steps (sx_k_res_fwd).  (Written out in one body: with the loads behind a second level
+// of inlined functions sx_k_res_fwd came out two registers wider.)
+template <bool ROW = true, class Cell>
+__device__ __forceinline__ void sx_forcing_at(const SxDeviceArrays& A, int t, Cell c, float& p, float& e) {
     const size_t npad = (size_t)A.npad;
-    if (A.prcp16 == nullptr) { p = sx_row_load(A.prcp + (size_t)t * npad, kb); e = sx_row_load(A.pet + (size_t)t * npad, kb); return; }
-    p = sx_prcp_decode(A, sx_row_load_u16(A.prcp16 + (size_t)t * npad, kb >> 1));
+    if (A.prcp16 == nullptr) {
+        if (ROW) { p = sx_row_load(A.prcp + (size_t)t * npad, c); e = sx_row_load(A.pet + (size_t)t * npad, c); }
+        else { p = A.prcp[(size_t)t * npad + c]; e = A.pet[(size_t)t * npad + c]; }
+        return;
+    }
+    p = sx_prcp_decode(A, ROW ? sx_row_load_u16(A.prcp16 + (size_t)t * npad, c >> 1) : (unsigned)A.prcp16[(size_t)t * npad + c]);
     const int q = t + A.hour0;
-    const float D = sx_row_load(A.petd + (size_t)(q / 24) * npad, kb);
-    e = D < 0.f ? D : D * ((sx_cfloat*)A.pet_ratio)[q % 24];
+    const float D = ROW ? sx_row_load(A.petd + (size_t)(q / 24) * npad, c) : A.petd[(size_t)(q / 24) * npad + c];
+    e = D < 0.f ? D : D * (ROW ? ((sx_cfloat*)A.pet_ratio)[q % 24] : A.pet_ratio[q % 24]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -459,20 +496,12 @@ void sx_k_vert_fwd(SxDeviceArrays A, int t0, int T) {
     if (k >= A.k1) return;
     const size_t npad = (size_t)A.npad;
 
+    const SxPlanCell<> cell{A, k};
     SxCellParams P;
     float hi = 0.f, hp = 0.f, hft = 0.f, hst = 0.f;
-    P.ci = (ST == 2 || ST == 3) ? A.ci[k] : 1.f;
-    P.cp = A.cp[k];
-    P.cft = A.cft[k];
-    P.cst = (ST == 3) ? A.cst[k] : 1.f;
-    P.exc = (ST != 4) ? A.exc[k] : 0.f;
-    sx_cell_params_init(P);
-    P.cft_m4 = sx_pow_m4(P.cft);
-    P.cst_m4 = (ST == 3) ? sx_pow_m4(P.cst) : 1.f;
-    if (ST == 2 || ST == 3) hi = A.hi[k];
-    hp = A.hp[k];
-    hft = A.hft[k];
-    if (ST == 3) hst = A.hst[k];
+    sx_cell_params<ST>(cell, P);
+    sx_fwd_powers<ST>(P);
+    sx_levels_in<ST>(cell, hi, hp, hft, hst);
 
     // rows are wave-uniform (sx_row_load / sx_row_store): the vector unit does no address arithmetic in the time loop
     const unsigned kb = (unsigned)k * 4u;
@@ -503,10 +532,7 @@ void sx_k_vert_fwd(SxDeviceArrays A, int t0, int T) {
         }
         sx_row_store4<SX_NT>(A.qtT + (size_t)tq * npad * 4, kb * 4u, q[0], q[1], q[2], q[3]);
     }
-    if (ST == 2 || ST == 3) A.hi[k] = hi;
-    A.hp[k] = hp;
-    A.hft[k] = hft;
-    if (ST == 3) A.hst[k] = hst;
+    sx_levels_out<ST>(cell, hi, hp, hft, hst);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -514,11 +540,7 @@ void sx_k_vert_fwd(SxDeviceArrays A, int t0, int T) {
 // forward_db.f90:10271-10316).  Same thread-per-cell time march, T4 qt, three tapes (husl1, husl2, hlsl).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ SxVicParams sx_vic_load(const SxDeviceArrays& A, int k) {
-    SxVicParams P;
-    P.b = A.ci[k]; P.cusl1 = A.cp[k]; P.cusl2 = A.cft[k]; P.clsl = A.cst[k]; P.ks = A.exc[k];
-    P.ds = A.px[0][k]; P.dsm = A.px[1][k]; P.ws = A.px[2][k];
-    sx_vic_derive(P);
-    return P;
+    return sx_vic_params(SxPlanCell<>{A, k});
 }
 // Same shape as the GR kernels: wave-uniform rows through buffer descriptors, forcing one step ahead (SxForcing), streaming stores
 // of the tapes, qt as one float4 per four steps; the reverse kernel prefetches the three taped levels and qt_b a step ahead.
@@ -573,10 +595,10 @@ __global__ __launch_bounds__(SX_VBLOCK, SX_VADJ_WAVES_VIC) void sx_k_vert_adj_vi
     const SxVicParams P = sx_vic_load(A, k);
     float cusl2_m4, cusl2_m5;
     sx_pow_m4_m5(P.cusl2, &cusl2_m4, &cusl2_m5);
+    const SxPlanCell<true> grad{A, k};
     SxVicGrads G;
-    G.b_b = A.ci_b[k]; G.cusl1_b = A.cp_b[k]; G.cusl2_b = A.cft_b[k]; G.clsl_b = A.cst_b[k]; G.ks_b = A.exc_b[k];
-    G.ds_b = A.px_b[0][k]; G.dsm_b = A.px_b[1][k]; G.ws_b = A.px_b[2][k];
-    G.husl1_b = A.hi_b[k]; G.husl2_b = A.hp_b[k]; G.hlsl_b = A.hft_b[k];
+    sx_vic_fields_in(grad, G.b_b, G.cusl1_b, G.cusl2_b, G.clsl_b, G.ks_b, G.ds_b, G.dsm_b, G.ws_b);
+    sx_vic_levels_in(grad, G.husl1_b, G.husl2_b, G.hlsl_b);
     const unsigned kb = (unsigned)k * 4u;
     SxForcing<CF> F(A, kb, t0 + T - 1);
     float n_h1 = 0.f, n_h2 = 0.f, n_hl = 0.f, n_q = 0.f;
@@ -595,9 +617,8 @@ __global__ __launch_bounds__(SX_VBLOCK, SX_VADJ_WAVES_VIC) void sx_k_vert_adj_vi
         if (tt > 0) fetch(tt - 1, false);
         sx_vic_step_b(P, cusl2_m4, cusl2_m5, F.prcp(), F.pet(), h1, h2, hl, q_b, G);
     }
-    A.ci_b[k] = G.b_b; A.cp_b[k] = G.cusl1_b; A.cft_b[k] = G.cusl2_b; A.cst_b[k] = G.clsl_b; A.exc_b[k] = G.ks_b;
-    A.px_b[0][k] = G.ds_b; A.px_b[1][k] = G.dsm_b; A.px_b[2][k] = G.ws_b;
-    A.hi_b[k] = G.husl1_b; A.hp_b[k] = G.husl2_b; A.hft_b[k] = G.hlsl_b;
+    sx_vic_fields_out(grad, G.b_b, G.cusl1_b, G.cusl2_b, G.clsl_b, G.ks_b, G.ds_b, G.dsm_b, G.ws_b);
+    sx_vic_levels_out(grad, G.husl1_b, G.husl2_b, G.hlsl_b);
 }
 
 // vic-a with tangents (VIC_A_FORWARD_D): tangents of the parameters / levels live in the gradient arrays
@@ -608,8 +629,7 @@ __global__ __launch_bounds__(SX_VBLOCK) void sx_k_vert_fwd_vic_d(SxDeviceArrays 
     const size_t npad = (size_t)A.npad;
     const SxVicParams P = sx_vic_load(A, k);
     SxVicTan D;
-    D.b_d = A.ci_b[k]; D.cusl1_d = A.cp_b[k]; D.cusl2_d = A.cft_b[k]; D.clsl_d = A.cst_b[k]; D.ks_d = A.exc_b[k];
-    D.ds_d = A.px_b[0][k]; D.dsm_d = A.px_b[1][k]; D.ws_d = A.px_b[2][k];
+    sx_vic_fields_in(SxPlanCell<true>{A, k}, D.b_d, D.cusl1_d, D.cusl2_d, D.clsl_d, D.ks_d, D.ds_d, D.dsm_d, D.ws_d);
     float cusl2_m4, cusl2_m5;
     sx_pow_m4_m5(P.cusl2, &cusl2_m4, &cusl2_m5);
     SxVD husl1 = sx_vd(A.hi[k], A.hi_b[k]), husl2 = sx_vd(A.hp[k], A.hp_b[k]), hlsl = sx_vd(A.hft[k], A.hft_b[k]);
@@ -636,26 +656,17 @@ __global__ __launch_bounds__(SX_VBLOCK) void sx_k_vert_fwd_d(SxDeviceArrays A, i
     if (k >= A.k1) return;
     const size_t npad = (size_t)A.npad;
     SxCellParams P;
-    P.ci = (ST == 2 || ST == 3) ? A.ci[k] : 1.f;
-    P.cp = A.cp[k];
-    P.cft = A.cft[k];
-    P.cst = (ST == 3) ? A.cst[k] : 1.f;
-    P.exc = (ST != 4) ? A.exc[k] : 0.f;
-    sx_cell_params_init(P);
+    sx_cell_params<ST>(SxPlanCell<>{A, k}, P);
     SxAdjParams Q;
-    Q.cst_m5 = 1.f;
-    sx_pow_m4_m5(P.cft, &P.cft_m4, &Q.cft_m5);
-    P.cst_m4 = 1.f;
-    if (ST == 3) sx_pow_m4_m5(P.cst, &P.cst_m4, &Q.cst_m5);
-    Q.dcft2 = sx_mkdiv(P.cft * P.cft);
-    Q.dcst2 = sx_mkdiv(P.cst * P.cst);
-    Q.dcp2 = sx_mkdiv(P.cp * P.cp);
+    sx_adj_params<ST>(P, Q);
     SxTanParams D;
     D.ci_d = (ST == 2 || ST == 3) ? A.ci_b[k] : 0.f;
     D.cp_d = A.cp_b[k];
     D.cft_d = A.cft_b[k];
     D.cst_d = (ST == 3) ? A.cst_b[k] : 0.f;
     D.exc_d = (ST != 4) ? A.exc_b[k] : 0.f;
+    // the levels with their tangents stay written out here: through sx_levels_in / _out over a (value, tangent) source this kernel's
+    // code came out different (operands of four additions swapped in gr-c, a handful of instructions more or less elsewhere)
     SxDual hi = sx_mk(0.f, 0.f), hp, hft, hst = sx_mk(0.f, 0.f);
     if (ST == 2 || ST == 3) hi = sx_mk(A.hi[k], A.hi_b[k]);
     hp = sx_mk(A.hp[k], A.hp_b[k]);
@@ -1218,20 +1229,9 @@ void sx_k_vert_adj(SxDeviceArrays A, int t0, int T) {
     if (k >= A.k1) return;
     const size_t npad = (size_t)A.npad;
     SxCellParams P;
-    P.ci = (ST == 2 || ST == 3) ? A.ci[k] : 1.f;
-    P.cp = A.cp[k];
-    P.cft = A.cft[k];
-    P.cst = (ST == 3) ? A.cst[k] : 1.f;
-    P.exc = (ST != 4) ? A.exc[k] : 0.f;
-    sx_cell_params_init(P);
+    sx_cell_params<ST>(SxPlanCell<>{A, k}, P);
     SxAdjParams Q;
-    Q.cst_m5 = 1.f;
-    sx_pow_m4_m5(P.cft, &P.cft_m4, &Q.cft_m5);
-    P.cst_m4 = 1.f;
-    if (ST == 3) sx_pow_m4_m5(P.cst, &P.cst_m4, &Q.cst_m5);
-    Q.dcft2 = sx_mkdiv(P.cft * P.cft);
-    Q.dcst2 = sx_mkdiv(P.cst * P.cst);
-    Q.dcp2 = sx_mkdiv(P.cp * P.cp);
+    sx_adj_params<ST>(P, Q);
     SxCellGrads G;
     G.ci_b = (ST == 2 || ST == 3) ? A.ci_b[k] : 0.f;
     G.cp_b = A.cp_b[k];

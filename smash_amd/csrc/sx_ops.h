@@ -11,6 +11,7 @@
 // libm calls are replaced by the sx_math.h routines (see its header for the parity argument).
 #pragma once
 
+#include "sx_fields.h"
 #include "sx_math.h"
 
 #define SX_DEV __device__ __forceinline__
@@ -33,6 +34,72 @@ SX_DEV void sx_cell_params_init(SxCellParams& P) {
     P.dci = sx_mkdiv(P.ci);
     P.dcft = sx_mkdiv(P.cft);
     P.dcst = sx_mkdiv(P.cst);
+}
+
+// ---- cell set-up from a field source ---------------------------------------------------------------------------------------------
+// A field source is a callable src(slot) -> the value of that slot (sx_fields.h) for the thread's cell, a sink a callable
+// dst(slot, value).  Two sources exist: the plan's per-cell vectors (SxPlanCell, sx_kernels.h) and the sample-or-base value of the
+// ensemble path (sx_ens_val, sx_ensemble.h).  Every forward, tangent and adjoint kernel of the GR structures sets its cell up here.
+template <int ST, class Src>
+SX_DEV void sx_cell_params(const Src& src, SxCellParams& P) {
+    P.ci = (ST == 2 || ST == 3) ? src(SX_SLOT_CI) : 1.f;
+    P.cp = src(SX_SLOT_CP);
+    P.cft = src(SX_SLOT_CFT);
+    P.cst = (ST == 3) ? src(SX_SLOT_CST) : 1.f;
+    P.exc = (ST != 4) ? src(SX_SLOT_EXC) : 0.f;
+    sx_cell_params_init(P);
+}
+template <int ST>
+SX_DEV void sx_fwd_powers(SxCellParams& P) {
+    P.cft_m4 = sx_pow_m4(P.cft);
+    P.cst_m4 = (ST == 3) ? sx_pow_m4(P.cst) : 1.f;
+}
+// reservoir levels in and out: hi only where the structure has an interception store, hst only for gr-c
+template <int ST, class Src>
+SX_DEV void sx_levels_in(const Src& src, float& hi, float& hp, float& hft, float& hst) {
+    if (ST == 2 || ST == 3) hi = src(SX_SLOT_HI);
+    hp = src(SX_SLOT_HP);
+    hft = src(SX_SLOT_HFT);
+    if (ST == 3) hst = src(SX_SLOT_HST);
+}
+template <int ST, class Dst>
+SX_DEV void sx_levels_out(const Dst& dst, float hi, float hp, float hft, float hst) {
+    if (ST == 2 || ST == 3) dst(SX_SLOT_HI, hi);
+    dst(SX_SLOT_HP, hp);
+    dst(SX_SLOT_HFT, hft);
+    if (ST == 3) dst(SX_SLOT_HST, hst);
+}
+
+// ---- linear routing of one cell, step by step (the per-lane routes sx_k_ens_route_fwd and sx_k_res_fwd) ----------------------------
+// upstream_discharge + linear_routing + the q update of md_forward_structure.f90:150-156 in the reference's operation order, with the
+// per-cell invariants of md_routing_operator.f90:55-56,75.  sx_k_prep_routing stores a, f and the denominator for the group kernels,
+// whose float4 form behind the LDS exchange stays written out in sx_route_fwd_group (a function carved out of that body would change
+// its schedule); sx_div4 is four sx_div (sx_math.h), so the scalar quotients here are the same bits.
+struct SxRouteCell {
+    float a, f, dt, dx;     // exp(-dt / (60 lr)), real(flwacc - 1)
+    bool hasup;
+    SxDiv dden, ddt;        // exact division by 0.001 dx dx f (dden.d is that denominator) and by dt
+};
+template <class Arrays>     // SxDeviceArrays (sx_kernels.h): dt, dx, flwacc
+SX_DEV SxRouteCell sx_route_cell(const Arrays& A, float lr, int k) {
+    SxRouteCell R;
+    R.a = sx_expf(-A.dt / (lr * 60.f));
+    const int facc = A.flwacc[k];
+    R.f = (float)(facc - 1);
+    R.hasup = facc > 1;
+    R.dt = A.dt; R.dx = A.dx;
+    R.dden = sx_mkdiv(0.001f * A.dx * A.dx * R.f);
+    R.ddt = sx_mkdiv(R.dt);
+    return R;
+}
+// sum: the upstream cells' discharge of this step added in D8 order, qt: the cell's lateral inflow; returns its discharge
+SX_DEV float sx_route_step(const SxRouteCell& R, float sum, float qt, float& hlr) {
+    const float qup = R.hasup ? sx_div(sum * R.dt, R.dden) : 0.f;
+    const float hr_imd = hlr + qup;
+    const float hnew = hr_imd * R.a;
+    const float qro = hr_imd - hnew;
+    hlr = hnew;
+    return sx_div((qt + qro * R.f) * R.dx * R.dx * 0.001f, R.ddt);
 }
 
 // everything gr_production computes, kept for the adjoint so tanh / the two divisions are evaluated once
@@ -332,6 +399,17 @@ struct SxAdjParams {   // extra per-cell invariants of the adjoint
     float cft_m5, cst_m5;          // powf(ct, -5)
     SxDiv dcft2, dcst2, dcp2;      // exact division by cft**2, cst**2, cp**2
 };
+// the adjoint's and the tangent's invariants; both powers of a base come from one logarithm, so P's forward powers are set here too
+template <int ST>
+SX_DEV void sx_adj_params(SxCellParams& P, SxAdjParams& Q) {
+    Q.cst_m5 = 1.f;
+    sx_pow_m4_m5(P.cft, &P.cft_m4, &Q.cft_m5);
+    P.cst_m4 = 1.f;
+    if (ST == 3) sx_pow_m4_m5(P.cst, &P.cst_m4, &Q.cst_m5);
+    Q.dcft2 = sx_mkdiv(P.cft * P.cft);
+    Q.dcst2 = sx_mkdiv(P.cst * P.cst);
+    Q.dcp2 = sx_mkdiv(P.cp * P.cp);
+}
 
 // still (wave-uniform): every lane is in a still step (sx_is_still) -- prcp = pet = 0 then, pr + perc = +0 and of
 // GR_PRODUCTION_B only the percolation term reaches hp_b (pn_b and en_b are read by nothing: GR_INTERCEPTION_B takes neither

@@ -11,6 +11,7 @@
 // (the correctly rounded quotient for the normal-range operands the operators produce, 6 instructions instead of 11).
 #pragma once
 
+#include "sx_fields.h"
 #include "sx_math.h"
 
 #ifndef SX_DEV
@@ -30,6 +31,34 @@ SX_DEV void sx_vic_derive(SxVicParams& P) {
     P.d11 = sx_mkdiv(P.cusl1 * P.cusl1); P.d22 = sx_mkdiv(P.cusl2 * P.cusl2); P.dll = sx_mkdiv(P.clsl * P.clsl);
 }
 struct SxVicGrads { float b_b, cusl1_b, cusl2_b, clsl_b, ks_b, ds_b, dsm_b, ws_b, husl1_b, husl2_b, hlsl_b; };
+
+// vic-a's eight parameters and three levels from a field source / to a sink (sx_ops.h), by the slots sx_fields.h gives them.  The
+// parameters, their gradients (SxVicGrads) and their tangents (SxVicTan) all come and go through these.
+template <class Src>
+SX_DEV void sx_vic_fields_in(const Src& src, float& b, float& cusl1, float& cusl2, float& clsl, float& ks, float& ds, float& dsm, float& ws) {
+    b = src(SX_SLOT_CI); cusl1 = src(SX_SLOT_CP); cusl2 = src(SX_SLOT_CFT); clsl = src(SX_SLOT_CST); ks = src(SX_SLOT_EXC);
+    ds = src(SX_SLOT_PX0); dsm = src(SX_SLOT_PX1); ws = src(SX_SLOT_PX2);
+}
+template <class Dst>
+SX_DEV void sx_vic_fields_out(const Dst& dst, float b, float cusl1, float cusl2, float clsl, float ks, float ds, float dsm, float ws) {
+    dst(SX_SLOT_CI, b); dst(SX_SLOT_CP, cusl1); dst(SX_SLOT_CFT, cusl2); dst(SX_SLOT_CST, clsl); dst(SX_SLOT_EXC, ks);
+    dst(SX_SLOT_PX0, ds); dst(SX_SLOT_PX1, dsm); dst(SX_SLOT_PX2, ws);
+}
+template <class Src>
+SX_DEV void sx_vic_levels_in(const Src& src, float& husl1, float& husl2, float& hlsl) {
+    husl1 = src(SX_SLOT_HI); husl2 = src(SX_SLOT_HP); hlsl = src(SX_SLOT_HFT);
+}
+template <class Dst>
+SX_DEV void sx_vic_levels_out(const Dst& dst, float husl1, float husl2, float hlsl) {
+    dst(SX_SLOT_HI, husl1); dst(SX_SLOT_HP, husl2); dst(SX_SLOT_HFT, hlsl);
+}
+template <class Src>
+SX_DEV SxVicParams sx_vic_params(const Src& src) {
+    SxVicParams P;
+    sx_vic_fields_in(src, P.b, P.cusl1, P.cusl2, P.clsl, P.ks, P.ds, P.dsm, P.ws);
+    sx_vic_derive(P);
+    return P;
+}
 
 // ---------------------------------------------------------------- forward
 // What the forward infiltration of a reverse step hands to its adjoint (round 3): the two bases' logarithms and the two powers.  The
