@@ -18,7 +18,8 @@ Every case is rebuilt from its id alone:
                                   full (husl1 = husl2 = 1, one step past the box) on one random half -- the only way to the clamp
                                   wusl >= cusl - 1e-6 and to iflc + prcp >= iflm, which no single field at a bound reaches.
 Observations are the oracle's discharge at parameters + 10 % (no field at a bound); the tangent direction is 0.01 x every
-parameter of the structure, with a zero state direction."""
+parameter of the structure, with a zero state direction.  tangent_extras adds, per case, the same direction without ci (gr-b, gr-c)
+and the direction of the field on the bound alone (states included), with the oracle's answers along them."""
 from __future__ import annotations
 
 import types
@@ -148,6 +149,52 @@ def build(cid):
     d = {k: np.asfortranarray((np.float32(0.01) * P[k] if k in ps else np.zeros_like(P[k])).astype(np.float32)) for k in synth.PARAM_NAMES}
     return types.SimpleNamespace(id=cid, structure=structure, dt=DT, nt=NT, mesh=m, prcp=prcp, pet=pet, qobs=qobs, params=P, states=S,
                                  opts={}, direction=d)
+
+
+def without_ci(g):
+    """Case g with ci's plane of the composite direction zeroed.  The forcing's PET is exactly zero at night, which puts the
+    interception operator of gr-b and gr-c on the kink of min(pet, prcp + hi ci) (tests/tangent_field_cases.py): along ci the fp32
+    oracle is 5 .. 40 % away from the fp64 truth, and that noise lifts the composite direction's bar to 1e-4 .. 1e-3.  Without ci in
+    the direction the bar is back at 3e-7 .. 5e-6."""
+    d = dict(g.direction, ci=np.zeros_like(g.direction["ci"]))
+    return types.SimpleNamespace(**dict(vars(g), id=g.id + " no-ci", direction=d))
+
+
+def floor_copy(g):
+    """Case g with every exactly zero PET value at tangent_field_cases.PET_FLOOR: off the interception kink."""
+    import tangent_field_cases as tf
+    return types.SimpleNamespace(**dict(vars(g), id=g.id + " floor", pet=tf.floor_pet(g.pet)))
+
+
+def tangent_extras(g):
+    """The tangent directions of case g beyond its composite one, each with the oracle's answers along it: a list of
+    (label, case, (params_d, states_d), field, ref32, ref64, grad32, truth) where case is g or its floor copy, field the lone field
+    of the direction (None: the composite direction without ci), ref32 / ref64 the dicts of tangent_field_cases.oracle_tangent,
+    grad32 the fp32 oracle's gradient plane of field on a floor copy (None: the case's own adjoint outputs hold it) and truth whether
+    the truth rule applies (the fp32 oracle within tangent_field_cases.E_REF_CAP of the fp64 truth on every gauge).
+      * gr-b, gr-c, every case: the composite direction without ci (without_ci);
+      * every B: case: tangent_field_cases.field_direction of the field on the bound, parameter or state.  It always takes the
+        adjoint-tangent identity; the truth rule where truth;
+      * the ci and hi cases of gr-b and gr-c: the same direction once more on the floor copy of the case, truth rule included."""
+    import tangent_field_cases as tf
+    kind, structure, *rest = g.id.split(":")
+    zero_states = {k: np.zeros_like(v) for k, v in g.states.items()}
+    out = []
+
+    def add(label, case, direction, field, grad32=None):
+        r32, r64 = tf.oracle_tangent(case, direction), tf.oracle_tangent(case, direction, fp64=True)
+        out.append((label, case, direction, field, r32, r64, grad32, field is None or max(tf.e_ref(r32, r64)) <= tf.E_REF_CAP))
+
+    if "ci" in gu.STRUCT_PARAMS[structure]:
+        add(g.id + " no-ci", g, (without_ci(g).direction, zero_states), None)
+    if kind == "B":
+        field = rest[0]
+        add(f"{g.id} lone {field}", g, tf.field_direction(g, field), field)
+        if field in ("ci", "hi"):
+            gf = floor_copy(g)
+            add(f"{gf.id} lone {field}", gf, tf.field_direction(gf, field), field, grad32=tf.oracle_gradient(gf)[field])
+            assert out[-1][-1], (gf.id, tf.e_ref(*out[-1][4:6]))
+    return out
 
 
 def oracle_outputs(g, fp64=False, kinds=("fwd", "adj", "tan")):

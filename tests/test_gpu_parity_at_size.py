@@ -8,7 +8,9 @@ Bars (fixed before the first run on the card, not tuned after it):
   * exact-libm build (SMASHX_EXACT_LIBM=1, run by tests/test_gpu_exact.py): BIT-IDENTICAL to the fp32 oracle on every forward and
     adjoint output -- discharge per gauge, cost, final states, every gradient field of the structure (_compare_with_oracle's rule).
     The tangent outputs are not held to bit-identity: no test holds the exact build's tangent to it today (the tangent sweep sums
-    the cost derivative in its own order), so they take the default-build rule below in both builds.
+    the cost derivative in its own order), so they take the default-build rule below in both builds.  What holds the tangent in
+    both builds is tests/test_gpu_tangent_fields.py: every field's own direction against the fp64 truth and against the adjoint
+    sweep of the same build.
   * default build: per output o, e_hip = rel_l2(hip, truth64) <= 2 e_ref + 1e-6 with e_ref = rel_l2(oracle32, truth64) -- the
     timed build is no farther from the exact answer than the reference is, within a factor 2.  truth64 = the same statements in
     double (oracle/liboracle64.so).  Costs: |hip - truth| <= 2 |ref - truth| + 3e-7 (the floor of golden_util.tol_cost).
