@@ -1278,8 +1278,9 @@ int smashx_set_forcing_layout(smashx_plan* p, const smashx_forcing_layout* lay) 
     }
     if (lay->compact) {
         if (p->cfg.dt != 3600.f) return fail(SMASHX_E_UNSUPPORTED, "compact forcing: the daily-PET form is defined for dt = 3600 s");
-        if (!(lay->prcp_factor > 0.f) || lay->pet_hour0 < 0 || lay->pet_hour0 > 23) return fail(SMASHX_E_ARG, "bad prcp_factor / pet_hour0");
-        for (int h = 0; h < 24; ++h) if (!(lay->pet_ratio[h] >= 0.f)) return fail(SMASHX_E_ARG, "pet_ratio must be >= 0");
+        // (positive / non-negative AND finite: the vertical kernels tell "no lane is in a gap" from the stored words, SxForcing::no_gap)
+        if (!(lay->prcp_factor > 0.f) || __builtin_isinf(lay->prcp_factor) || lay->pet_hour0 < 0 || lay->pet_hour0 > 23) return fail(SMASHX_E_ARG, "bad prcp_factor / pet_hour0");
+        for (int h = 0; h < 24; ++h) if (!(lay->pet_ratio[h] >= 0.f) || __builtin_isinf(lay->pet_ratio[h])) return fail(SMASHX_E_ARG, "pet_ratio must be >= 0 and finite");
     }
     p->flay = *lay;
     return 0;

@@ -370,6 +370,12 @@ __global__ void sx_k_prep_routing(SxDeviceArrays A) {
 #ifndef SX_STILL
 #define SX_STILL 1
 #endif
+// A reverse step at which no lane of a wavefront is in a data gap takes the gap-free form of the step (sx_ops.h, NOGAP).
+// -DSX_GAPFREE=0 compiles the general form only (A/B builds).  The forward kernels have no such form: with it their loop, unrolled
+// by four, held eight bodies of the step and ran 9 % slower.
+#ifndef SX_GAPFREE
+#define SX_GAPFREE 1
+#endif
 #define SX_HIK 8             // steps per block of the interception level's checkpoint / rebuild (chunk offsets are multiples of 16)
 #ifndef SX_VADJ_NT
 #define SX_VADJ_NT 0
@@ -404,12 +410,17 @@ __device__ __forceinline__ float sx_prcp_decode(const SxDeviceArrays& A, unsigne
     return k == 65535u ? A.prcp_gap : v;
 }
 
-// Forcing cursor of one marching thread.  request() issues the loads of a step and returns at once; hold() -- called one step
-// later -- is where the wait lands (the words are pinned there, before the next request is issued), and prcp() / pet() decode the
-// held words.  Layouts: COMPACT = false: fp32 rows; true: u16 rain count + the day's PET + the hour's ratio.  The hour of day is
+// Forcing cursor of one marching thread.  request<.., S>() issues the loads of a step into register set S and returns at once;
+// hold<S>() -- called one step later -- is where the wait lands (the words are pinned there, before the next request is issued), and
+// prcp<S>() / pet<S>() decode the held words.  There are two sets and consecutive steps alternate between them: the step that computes
+// from set S requests the next one into set 1 - S, so nothing is copied from a "next" to a "held" register (the loops that march are
+// unrolled by an even count, or by two, to make S a compile-time index).  Only the day's PET of the compact layout is handed from set
+// to set, on the 23 steps of a day that load none.
+// Layouts: COMPACT = false: fp32 rows; true: u16 rain count + the day's PET + the hour's ratio.  The hour of day is
 // wave-uniform, so the day-change test is scalar work; the ratio is requested like a row, one step ahead (a load issued where it is
 // used drags the prefetched rows of the next step into this step's wait -- measured: vert_fwd 42 -> 55 ms, vert_adj 76 -> 97 ms).
 typedef const __attribute__((address_space(4))) float sx_cfloat;
+template <int S> struct SxSet { static constexpr int value = S; };      // a register set as a function argument (generic lambdas)
 template <bool COMPACT>
 struct SxForcing {
     const SxDeviceArrays& A;
@@ -417,18 +428,19 @@ struct SxForcing {
     const size_t npad;
     int h;                      // hour index of the step the next request() is for
     const char* prow; const char* erow;      // rows of that step (wave-uniform running pointers: one scalar add per step and stream)
-    unsigned p_n, p_w; float e_n, e_w, r_n, r_w;
+    unsigned p_[2]; float e_[2], r_[2];
     __device__ __forceinline__ SxForcing(const SxDeviceArrays& A_, unsigned kb_, int t_first)
         : A(A_), kb(kb_), npad((size_t)A_.npad), h(COMPACT ? (t_first + A_.hour0) % 24 : 0),
           prow(COMPACT ? (const char*)(A_.prcp16 + (size_t)t_first * A_.npad) : (const char*)(A_.prcp + (size_t)t_first * A_.npad)),
           erow(COMPACT ? nullptr : (const char*)(A_.pet + (size_t)t_first * A_.npad)),
-          p_n(0u), p_w(0u), e_n(0.f), e_w(0.f), r_n(0.f), r_w(0.f) {}
+          p_{0u, 0u}, e_{0.f, 0.f}, r_{0.f, 0.f} {}
     // t: absolute time step (consecutive calls move by one step, forwards or BACKwards); first: nothing is held yet
-    template <int AUX, bool BACK> __device__ __forceinline__ void request(int t, bool first) {
+    // HANDED: the day's PET of the compact layout comes from the other set when this request loads none (false: set S keeps its own, hold_copy)
+    template <int AUX, bool BACK, int S, bool HANDED = true> __device__ __forceinline__ void request(int t, bool first) {
         const long step = (long)npad * (COMPACT ? 2 : 4) * (BACK ? -1 : 1);
         if (!COMPACT) {
-            p_n = __float_as_uint(sx_row_load<AUX>((const float*)prow, kb));
-            e_n = sx_row_load<AUX>((const float*)erow, kb);
+            p_[S] = __float_as_uint(sx_row_load<AUX>((const float*)prow, kb));
+            e_[S] = sx_row_load<AUX>((const float*)erow, kb);
             prow += step; erow += step;
             return;
         }
@@ -436,24 +448,42 @@ struct SxForcing {
         // and a 16-bit load result is zero-extended by an ALU instruction right behind the load -- a wait in the same step
         // (measured: vert_adj 76 -> 89 ms).  The ratio comes the same way, one broadcast dword: a scalar load would be waited for
         // on the spot as well.
-        p_n = __float_as_uint(sx_row_load<AUX>((const float*)prow, (kb >> 1) & ~3u));
+        p_[S] = __float_as_uint(sx_row_load<AUX>((const float*)prow, (kb >> 1) & ~3u));
         prow += step;
-        if (first || h == (BACK ? 23 : 0)) e_n = sx_row_load<AUX>(A.petd + (size_t)((t + A.hour0) / 24) * npad, kb);   // a new day
-        r_n = sx_row_load(A.pet_ratio + h, 0u);
+        if (first || h == (BACK ? 23 : 0)) e_[S] = sx_row_load<AUX>(A.petd + (size_t)((t + A.hour0) / 24) * npad, kb);   // a new day
+        else if (HANDED) e_[S] = e_[1 - S];
+        r_[S] = sx_row_load(A.pet_ratio + h, 0u);
         h = BACK ? (h == 0 ? 23 : h - 1) : (h == 23 ? 0 : h + 1);
     }
-    __device__ __forceinline__ void hold() {
-        p_w = p_n; e_w = e_n; r_w = r_n;
-        sx_pinu(p_w); sx_pin1(e_w);
-        if (COMPACT) sx_pin1(r_w);
+    template <int S> __device__ __forceinline__ void hold() {
+        sx_pinu(p_[S]); sx_pin1(e_[S]);
+        if (COMPACT) sx_pin1(r_[S]);
     }
-    __device__ __forceinline__ float prcp() const {
-        if (!COMPACT) return __uint_as_float(p_w);
-        return sx_prcp_decode(A, (p_w >> ((kb & 4u) << 2)) & 0xffffu);      // this lane's half of the dword (kb = 4 x cell)
+    // the vic-a kernels (at their register limits as they are) keep one held set: every request goes to set 1 and is copied to set 0 here
+    __device__ __forceinline__ void hold_copy() {
+        p_[0] = p_[1]; e_[0] = e_[1]; r_[0] = r_[1];
+        hold<0>();
     }
-    __device__ __forceinline__ float pet() const {
-        if (!COMPACT) return e_w;
-        return e_w < 0.f ? e_w : e_w * r_w;
+    template <int S> __device__ __forceinline__ unsigned count() const { return (p_[S] >> ((kb & 4u) << 2)) & 0xffffu; }   // this lane's half of the dword (kb = 4 x cell)
+    // this lane is in no data gap at the held step: prcp >= 0 and pet >= 0, told from the held words.  fp32 rows: the values themselves.
+    // Compact: the count is not the gap marker -- prcp is then count x prcp_c, a product of two finite non-negative numbers
+    // (smashx_set_forcing_layout refuses a factor that is not positive and finite) -- and the day's PET is zero or positive and finite
+    // (one class test: +-0, subnormal, normal) -- pet is then its product with the hour's ratio, which is >= 0 and finite (the same
+    // check), so it is >= 0 as well.  A day's PET of -0 is no gap day to the decode below either (-0 < 0 is false).
+    template <int S> __device__ __forceinline__ bool no_gap() const {
+        if (!COMPACT) return __uint_as_float(p_[S]) >= 0.f && e_[S] >= 0.f;
+        return count<S>() != 65535u && __builtin_amdgcn_classf(e_[S], 0x1e0);      // -0 | +0 | +subnormal | +normal
+    }
+    // NOGAP: no_gap() holds on this lane -- the decode's gap selects take the operand they would have taken
+    template <int S, bool NOGAP = false> __device__ __forceinline__ float prcp() const {
+        if (!COMPACT) return __uint_as_float(p_[S]);
+        if (NOGAP) return (float)count<S>() * A.prcp_c;                 // sx_prcp_decode with k != 65535
+        return sx_prcp_decode(A, count<S>());
+    }
+    template <int S, bool NOGAP = false> __device__ __forceinline__ float pet() const {
+        if (!COMPACT) return e_[S];
+        if (NOGAP) return e_[S] * r_[S];                                // e >= 0: not the gap day
+        return e_[S] < 0.f ? e_[S] : e_[S] * r_[S];
     }
 };
 
@@ -506,33 +536,40 @@ void sx_k_vert_fwd(SxDeviceArrays A, int t0, int T) {
     // rows are wave-uniform (sx_row_load / sx_row_store): the vector unit does no address arithmetic in the time loop
     const unsigned kb = (unsigned)k * 4u;
     SxForcing<CF> F(A, kb, t0);
-    if (T > 0) F.template request<SX_NT, false>(t0, true);
+    // step tt computes from forcing set tt & 1 (= the unroll index & 1) and requests step tt + 1 into the other one
+    auto step = [&](auto S, int tt) -> float {
+        constexpr int s = decltype(S)::value;
+        F.template hold<s>();                            // the wait for this step's forcing goes here, before the next loads
+        if (tt + 1 < T) F.template request<SX_NT, false, 1 - s>(t0 + tt + 1, false);
+        if (TAPE) {
+            const size_t o = (size_t)tt * npad;
+            if (ST == 2 || ST == 3) {     // the interception level: a full tape when it fits, else one checkpoint per SX_HIK steps
+                if (A.tape_hi) sx_row_store<SX_NT>(A.tape_hi + o, kb, hi);
+                else if ((tt % SX_HIK) == 0) sx_row_store<SX_NT>(A.ckpt_hi + (size_t)(tt / SX_HIK) * npad, kb, hi);
+            }
+            sx_row_store<SX_NT>(A.tape_hp + o, kb, hp);
+            sx_row_store<SX_NT>(A.tape_hft + o, kb, hft);
+            if (ST == 3) sx_row_store<SX_NT>(A.tape_hst + o, kb, hst);
+        }
+        const float prcp = F.template prcp<s>(), pet = F.template pet<s>();
+        const bool still = SX_STILL && sx_wave_all(sx_is_still<ST>(prcp, pet, hi, hp));      // wave-uniform
+        return sx_vertical_step<ST>(P, prcp, pet, hi, hp, hft, hst, still);
+    };
+    if (T > 0) F.template request<SX_NT, false, 0>(t0, true);
     for (int tq = 0; tq * 4 < T; ++tq) {
         float q[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int tt = tq * 4 + i;
-            if (tt < T) {
-                F.hold();                            // the wait for this step's forcing goes here, before the next loads
-                if (tt + 1 < T) F.template request<SX_NT, false>(t0 + tt + 1, false);
-                const float prcp = F.prcp(), pet = F.pet();
-                if (TAPE) {
-                    const size_t o = (size_t)tt * npad;
-                    if (ST == 2 || ST == 3) {     // the interception level: a full tape when it fits, else one checkpoint per SX_HIK steps
-                        if (A.tape_hi) sx_row_store<SX_NT>(A.tape_hi + o, kb, hi);
-                        else if ((tt % SX_HIK) == 0) sx_row_store<SX_NT>(A.ckpt_hi + (size_t)(tt / SX_HIK) * npad, kb, hi);
-                    }
-                    sx_row_store<SX_NT>(A.tape_hp + o, kb, hp);
-                    sx_row_store<SX_NT>(A.tape_hft + o, kb, hft);
-                    if (ST == 3) sx_row_store<SX_NT>(A.tape_hst + o, kb, hst);
-                }
-                const bool still = SX_STILL && sx_wave_all(sx_is_still<ST>(prcp, pet, hi, hp));      // wave-uniform
-                q[i] = sx_vertical_step<ST>(P, prcp, pet, hi, hp, hft, hst, still);
-            }
+            if (tt < T) q[i] = (i & 1) ? step(SxSet<1>{}, tt) : step(SxSet<0>{}, tt);
         }
         sx_row_store4<SX_NT>(A.qtT + (size_t)tq * npad * 4, kb * 4u, q[0], q[1], q[2], q[3]);
     }
-    sx_levels_out<ST>(cell, hi, hp, hft, hst);
+    // (a cell index the compiler cannot match with the one sx_levels_in used: the addresses of these stores are formed here instead of
+    // living in registers across the time loop)
+    unsigned ke = (unsigned)k;
+    sx_pinu(ke);
+    sx_levels_out<ST>(SxPlanCell<>{A, (int)ke}, hi, hp, hft, hst);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -558,22 +595,22 @@ __global__ __launch_bounds__(SX_VBLOCK, TAPE ? SX_VFWD_WAVES_VIC : 1) void sx_k_
     float husl1 = A.hi[k], husl2 = A.hp[k], hlsl = A.hft[k];
     const unsigned kb = (unsigned)k * 4u;
     SxForcing<CF> F(A, kb, t0);
-    if (T > 0) F.template request<SX_NT, false>(t0, true);
+    if (T > 0) F.template request<SX_NT, false, 1, false>(t0, true);
     for (int tq = 0; tq * 4 < T; ++tq) {
         float q[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int tt = tq * 4 + i;
             if (tt < T) {
-                F.hold();
-                if (tt + 1 < T) F.template request<SX_NT, false>(t0 + tt + 1, false);
+                F.hold_copy();
+                if (tt + 1 < T) F.template request<SX_NT, false, 1, false>(t0 + tt + 1, false);
                 if (TAPE) {
                     const size_t o = (size_t)tt * npad;
                     sx_row_store<SX_NT>(A.tape_hi + o, kb, husl1);
                     sx_row_store<SX_NT>(A.tape_hp + o, kb, husl2);
                     sx_row_store<SX_NT>(A.tape_hft + o, kb, hlsl);
                 }
-                q[i] = sx_vic_step(P, cusl2_m4, F.prcp(), F.pet(), husl1, husl2, hlsl);
+                q[i] = sx_vic_step(P, cusl2_m4, F.template prcp<0>(), F.template pet<0>(), husl1, husl2, hlsl);
             }
         }
         sx_row_store4<SX_NT>(A.qtT + (size_t)tq * npad * 4, kb * 4u, q[0], q[1], q[2], q[3]);
@@ -604,7 +641,7 @@ __global__ __launch_bounds__(SX_VBLOCK, SX_VADJ_WAVES_VIC) void sx_k_vert_adj_vi
     float n_h1 = 0.f, n_h2 = 0.f, n_hl = 0.f, n_q = 0.f;
     auto fetch = [&](int tt, bool first) {
         const size_t o = (size_t)tt * npad;
-        F.template request<SX_VADJ_NT, true>(t0 + tt, first);
+        F.template request<SX_VADJ_NT, true, 1, false>(t0 + tt, first);
         n_h1 = sx_row_load<SX_VADJ_NT>(A.tape_hi + o, kb); n_h2 = sx_row_load<SX_VADJ_NT>(A.tape_hp + o, kb);
         n_hl = sx_row_load<SX_VADJ_NT>(A.tape_hft + o, kb);
         n_q = sx_row_load(A.qtT + (size_t)(tt >> 2) * npad * 4 + (tt & 3), kb * 4u);
@@ -612,10 +649,10 @@ __global__ __launch_bounds__(SX_VBLOCK, SX_VADJ_WAVES_VIC) void sx_k_vert_adj_vi
     if (T > 0) fetch(T - 1, true);
     for (int tt = T - 1; tt >= 0; --tt) {
         float h1 = n_h1, h2 = n_h2, hl = n_hl, q_b = n_q;
-        F.hold();
+        F.hold_copy();
         sx_pin1(h1); sx_pin1(h2); sx_pin1(hl); sx_pin1(q_b);
         if (tt > 0) fetch(tt - 1, false);
-        sx_vic_step_b(P, cusl2_m4, cusl2_m5, F.prcp(), F.pet(), h1, h2, hl, q_b, G);
+        sx_vic_step_b(P, cusl2_m4, cusl2_m5, F.template prcp<0>(), F.template pet<0>(), h1, h2, hl, q_b, G);
     }
     sx_vic_fields_out(grad, G.b_b, G.cusl1_b, G.cusl2_b, G.clsl_b, G.ks_b, G.ds_b, G.dsm_b, G.ws_b);
     sx_vic_levels_out(grad, G.husl1_b, G.husl2_b, G.hlsl_b);
@@ -1247,7 +1284,9 @@ void sx_k_vert_adj(SxDeviceArrays A, int t0, int T) {
     // byte offset: no vector address arithmetic in the time loop
     const unsigned kb = (unsigned)k * 4u;
     SxForcing<CF> F(A, kb, t0 + T - 1);
-    float n_hi = 0.f, n_hp = 0.f, n_hft = 0.f, n_hst = 0.f, n_q = 0.f;
+    // two register sets of everything prefetched: step tt computes from set tt & 1 and fetches step tt - 1 into the other one, so a
+    // step opens with the wait and the pins and copies nothing
+    float n_hi[2] = {0.f, 0.f}, n_hp[2] = {0.f, 0.f}, n_hft[2] = {0.f, 0.f}, n_hst[2] = {0.f, 0.f}, n_q[2] = {0.f, 0.f};
     const bool hi_taped = (ST == 2 || ST == 3) && A.tape_hi != nullptr;       // wave-uniform
     // tape rows of the step the next fetch is for: running pointers, stepped back one row per fetch
     const size_t olast = (size_t)(T > 0 ? T - 1 : 0) * npad;
@@ -1255,20 +1294,43 @@ void sx_k_vert_adj(SxDeviceArrays A, int t0, int T) {
     const float* r_hp = A.tape_hp + olast;
     const float* r_hft = A.tape_hft + olast;
     const float* r_hst = (ST == 3) ? A.tape_hst + olast : nullptr;
-    auto fetch = [&](int tt, bool first) {
-        F.template request<SX_VADJ_NT, true>(t0 + tt, first);
-        if (hi_taped) { n_hi = sx_row_load<SX_VADJ_NT>(r_hi, kb); r_hi -= npad; }
-        n_hp = sx_row_load<SX_VADJ_NT>(r_hp, kb); n_hft = sx_row_load<SX_VADJ_NT>(r_hft, kb);
+    auto fetch = [&](auto S, int tt, bool first) {
+        constexpr int s = decltype(S)::value;
+        F.template request<SX_VADJ_NT, true, s>(t0 + tt, first);
+        if (hi_taped) { n_hi[s] = sx_row_load<SX_VADJ_NT>(r_hi, kb); r_hi -= npad; }
+        n_hp[s] = sx_row_load<SX_VADJ_NT>(r_hp, kb); n_hft[s] = sx_row_load<SX_VADJ_NT>(r_hft, kb);
         r_hp -= npad; r_hft -= npad;
-        if (ST == 3) { n_hst = sx_row_load<SX_VADJ_NT>(r_hst, kb); r_hst -= npad; }
-        n_q = sx_row_load(A.qtT + (size_t)(tt >> 2) * npad * 4 + (tt & 3), kb * 4u);
+        if (ST == 3) { n_hst[s] = sx_row_load<SX_VADJ_NT>(r_hst, kb); r_hst -= npad; }
+        n_q[s] = sx_row_load(A.qtT + (size_t)(tt >> 2) * npad * 4 + (tt & 3), kb * 4u);
     };
     // When the interception level is not taped (it depends on the forcing and ci only; the plan drops its tape when that is what
     // lets the whole period fit): each block of SX_HIK steps is marched forward once more from its checkpoint -- the same
     // sx_interception on the same operands, hence the same bits -- and the pre-step levels wait in this thread's LDS
     // column for the reverse steps of the block.
     __shared__ float s_hi[(ST == 2 || ST == 3) ? SX_HIK : 1][SX_VBLOCK];
-    if (T > 0) fetch(T - 1, true);
+    auto step = [&](auto S, int tt, int tt0) {
+        constexpr int s = decltype(S)::value;
+        __builtin_amdgcn_sched_barrier(0);          // a step is scheduled by itself, as when every step was a turn of the loop
+        F.template hold<s>();
+        sx_pin1(n_hp[s]); sx_pin1(n_hft[s]); sx_pin1(n_q[s]);
+        if (ST == 2 || ST == 3) sx_pin1(n_hi[s]);
+        if (ST == 3) sx_pin1(n_hst[s]);
+        if (tt > 0) fetch(SxSet<1 - s>{}, tt - 1, false);
+        const float hi = (ST == 2 || ST == 3) ? (hi_taped ? n_hi[s] : s_hi[tt - tt0][threadIdx.x]) : 0.f;
+        // wave-uniform, one ballot and a scalar branch each: no lane in a data gap -> the gap-free form of the step (sx_ops.h); every
+        // lane still -> its short form.  gr-b only: the second body costs 10 - 16 registers, which gr-b has to spare below its 96 and the
+        // others have not (gr-a, compact: 62 -> 73 = a wave less; gr-d: 56 -> 65 = a wave less; gr-c: 89 -> 96 and 72 B of scratch)
+        if (SX_GAPFREE && ST == 2 && sx_wave_all(F.template no_gap<s>())) {
+            const float prcp = F.template prcp<s, true>(), pet = F.template pet<s, true>();
+            const bool still = SX_STILL && sx_wave_all(sx_is_still<ST, true>(prcp, pet, hi, n_hp[s]));
+            sx_vertical_step_b<ST, true>(P, Q, prcp, pet, hi, n_hp[s], n_hft[s], n_hst[s], n_q[s], G, still);
+            return;
+        }
+        const float prcp = F.template prcp<s>(), pet = F.template pet<s>();
+        const bool still = SX_STILL && sx_wave_all(sx_is_still<ST>(prcp, pet, hi, n_hp[s]));
+        sx_vertical_step_b<ST>(P, Q, prcp, pet, hi, n_hp[s], n_hft[s], n_hst[s], n_q[s], G, still);
+    };
+    if (T > 0) { if ((T - 1) & 1) fetch(SxSet<1>{}, T - 1, true); else fetch(SxSet<0>{}, T - 1, true); }
     for (int tb = (T - 1) / SX_HIK; tb >= 0; --tb) {
         const int tt0 = tb * SX_HIK, len = min(SX_HIK, T - tt0);
         if ((ST == 2 || ST == 3) && !hi_taped) {
@@ -1282,24 +1344,25 @@ void sx_k_vert_adj(SxDeviceArrays A, int t0, int T) {
                 if (j < len && fp[j] >= 0.f && fe[j] >= 0.f) { float pn, ei; sx_interception(fp[j], fe[j], P.ci, P.dci, h, pn, ei); }
             }
         }
-        for (int tt = tt0 + len - 1; tt >= tt0; --tt) {
-            float hit = n_hi, hp = n_hp, hft = n_hft, hst = n_hst, q = n_q;
-            F.hold();
-            sx_pin1(hp); sx_pin1(hft); sx_pin1(q);
-            if (ST == 2 || ST == 3) sx_pin1(hit);
-            if (ST == 3) sx_pin1(hst);
-            if (tt > 0) fetch(tt - 1, false);
-            const float prcp = F.prcp(), pet = F.pet();
-            const float hi = (ST == 2 || ST == 3) ? (hi_taped ? hit : s_hi[tt - tt0][threadIdx.x]) : 0.f;
-            const bool still = SX_STILL && sx_wave_all(sx_is_still<ST>(prcp, pet, hi, hp));      // wave-uniform
-            sx_vertical_step_b<ST>(P, Q, prcp, pet, hi, hp, hft, hst, q, G, still);
+        // two steps per turn, odd then even (tt0 is even, so an odd step of the block has an even one below it); a block of an odd
+        // length -- only the last of the chunk -- opens with its single even step
+        int tt = tt0 + len - 1;
+        bool odd = (tt & 1) != 0;
+        while (tt >= tt0) {
+            if (odd) { step(SxSet<1>{}, tt, tt0); --tt; }
+            step(SxSet<0>{}, tt, tt0); --tt;
+            odd = true;
         }
     }
-    if (ST == 2 || ST == 3) { A.ci_b[k] = G.ci_b; A.hi_b[k] = G.hi_b; }
-    A.cp_b[k] = G.cp_b;
-    A.cft_b[k] = G.cft_b;
-    if (ST == 3) { A.cst_b[k] = G.cst_b; A.hst_b[k] = G.hst_b; }
-    if (ST != 4) A.exc_b[k] = G.exc_b;
-    A.hp_b[k] = G.hp_b;
-    A.hft_b[k] = G.hft_b;
+    // the addresses of these stores are formed here, from a cell index the compiler cannot match with the one the loads above used:
+    // otherwise it keeps the seven 64-bit addresses of the loads in registers across the whole time loop for the stores
+    unsigned ke = (unsigned)k;
+    sx_pinu(ke);
+    if (ST == 2 || ST == 3) { A.ci_b[ke] = G.ci_b; A.hi_b[ke] = G.hi_b; }
+    A.cp_b[ke] = G.cp_b;
+    A.cft_b[ke] = G.cft_b;
+    if (ST == 3) { A.cst_b[ke] = G.cst_b; A.hst_b[ke] = G.hst_b; }
+    if (ST != 4) A.exc_b[ke] = G.exc_b;
+    A.hp_b[ke] = G.hp_b;
+    A.hft_b[ke] = G.hft_b;
 }

@@ -225,10 +225,11 @@ SX_DEV float sx_vertical_step(const SxCellParams& P, float prcp, float pet, floa
 // Lanes in a data gap (prcp < 0 or pet < 0, md_forward_structure.f90:106) do not keep a wavefront from the short form: the general
 // step skips interception, production and exchange for them, and so does the short one, lane by lane (a gap every thousand cell-steps,
 // as in the synthetic forcing, otherwise sends 6 % of the wavefront-steps -- and a quarter of them would have been still -- the long way).
-template <int ST>
+template <int ST, bool NOGAP = false>
 SX_DEV bool sx_is_still(float prcp, float pet, float hi, float hp) {
     bool s = (prcp == 0.f) & (pet == 0.f) & (fabsf(hp) < 15.f);
     if (ST == 2 || ST == 3) s = s & (hi >= 0.f) & (hi <= 1.f);
+    if (NOGAP) return s;                            // the gap term below is false on every lane: s | false
     return s | !(prcp >= 0.f && pet >= 0.f);
 }
 
@@ -333,10 +334,16 @@ SX_DEV void sx_production_b(const SxProd& R, float pn, float& pn_b, float en, fl
 }
 
 // ht = pre-step level
+// NOGAP (here and below, the reverse step): the caller knows that no lane of the wavefront is in a data gap at this step
+// (SxForcing::no_gap, sx_kernels.h: prcp >= 0 and pet >= 0 on every lane), so "this lane is in a gap" is a compile-time false.  Each
+// place says what the general code would have chosen.
+template <bool NOGAP = false>
 SX_DEV void sx_transfer_b(float prcp, float pr, float& pr_b, float ct, const SxDiv& dct, const SxDiv& dct2, float ct_m4,
                           float ct_m5, float& ct_b, float ht, float& ht_b, float q_b) {
     float pr_imd = pr, g_pwx1 = 0.f, g_pwx3 = 0.f;
-    const bool gap = prcp < 0.f;
+    // NOGAP: prcp >= 0, so neither gap region runs: pr_imd stays pr, pr_b = pr_imd_b (the select's second operand), and htb / ct_b leave
+    // as the general part formed them
+    const bool gap = !NOGAP && prcp < 0.f;
     const bool any_gap = gap;
     if (any_gap) {
         if (gap) {
@@ -414,10 +421,12 @@ SX_DEV void sx_adj_params(SxCellParams& P, SxAdjParams& Q) {
 // still (wave-uniform): every lane is in a still step (sx_is_still) -- prcp = pet = 0 then, pr + perc = +0 and of
 // GR_PRODUCTION_B only the percolation term reaches hp_b (pn_b and en_b are read by nothing: GR_INTERCEPTION_B takes neither
 // branch and its quotients multiply prcp - ei - pn = 0); ci_b, cp_b, hi_b stay.
-template <int ST>
+template <int ST, bool NOGAP = false>
 SX_DEV void sx_vertical_step_b(const SxCellParams& P, const SxAdjParams& Q, float prcp, float pet, float hi, float hp,
                                float hft, float hst, float qt_b, SxCellGrads& G, bool still = false) {
-    const bool wet = prcp >= 0.f && pet >= 0.f;         // (per lane, also inside a still wavefront: its gap lanes take the dry path)
+    // (per lane, also inside a still wavefront: its gap lanes take the dry path.)  NOGAP: true on every lane -- both `wet` regions run
+    // unpredicated and the zeros that a gap lane keeps (ei .. l, h35, h25) are merged with nothing
+    const bool wet = NOGAP || (prcp >= 0.f && pet >= 0.f);
     float ei = 0.f, pn = 0.f, en = 0.f, pr = 0.f, perc = 0.f, l = 0.f, prr, prl = 0.f, prd = 0.f;
     float h35 = 0.f, h25 = 0.f;
     SxProd R;
@@ -441,8 +450,8 @@ SX_DEV void sx_vertical_step_b(const SxCellParams& P, const SxAdjParams& Q, floa
     if (ST != 4) {
         if (0.f < prd + l) { prd_b = qd_b; l_b = qd_b; }
     }
-    if (ST == 3) sx_transfer_b(prcp, prl, prl_b, P.cst, P.dcst, Q.dcst2, P.cst_m4, Q.cst_m5, G.cst_b, hst, G.hst_b, ql_b);
-    sx_transfer_b(prcp, prr, prr_b, P.cft, P.dcft, Q.dcft2, P.cft_m4, Q.cft_m5, G.cft_b, hft, G.hft_b, qr_b);
+    if (ST == 3) sx_transfer_b<NOGAP>(prcp, prl, prl_b, P.cst, P.dcst, Q.dcst2, P.cst_m4, Q.cst_m5, G.cst_b, hst, G.hst_b, ql_b);
+    sx_transfer_b<NOGAP>(prcp, prr, prr_b, P.cft, P.dcft, Q.dcft2, P.cft_m4, Q.cft_m5, G.cft_b, hft, G.hft_b, qr_b);
     if (ST == 1 || ST == 2) {
         pr_b = 0.1f * prd_b + 0.9f * prr_b;
         perc_b = 0.1f * prd_b + 0.9f * prr_b;
