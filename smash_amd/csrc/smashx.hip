@@ -30,6 +30,7 @@
 #include "sx_annmap.h"
 #include "sx_annhost.h"
 #include "sx_samplehost.h"
+#include "sx_tablehost.h"
 #include "sx_plan.h"
 #include "sx_selftest.h"
 
@@ -427,17 +428,14 @@ struct smashx_plan {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     smashx_timing timing{};
     int last_adjoint = 0;
-    // ensemble path (smashx_multiple_run): tables built and buffers allocated on first use, all its own
-    std::vector<signed char> h_flwdir;   // D8 codes of the whole grid (0 = none), kept for the upstream tables
-    // catchment means of the forcing (smashx_mean_forcing): D8 codes of EVERY cell of the grid, active or not (mask_upstream_cells follows
-    // them all), the per-gauge lists of plan cells on the device, the running sums between launches; built on first use
+    // D8 codes of EVERY cell of the grid, active or not (0 = none): the forest of the sample paths reads them at the plan's cells,
+    // mask_upstream_cells follows them all.  The host tables below are built by sx_tablehost.h on first use
     std::vector<signed char> h_flwdir_grid;
+    // catchment means of the forcing (smashx_mean_forcing): the per-gauge lists of plan cells, the running sums between launches
     struct MeanForcing {
         int state = 0;                   // 0 = not built, 1 = ready, 2 = refused (a catchment leaves the active cells)
         std::string refusal;
-        std::vector<int> count;          // ng: cells of the catchment
-        std::vector<int> begin;          // ng + 1: its list in h_list, padded with -1 to whole blocks of 64 entries
-        std::vector<int> h_list;         // the lists as uploaded (smashx_prcp_indices builds its own from them)
+        SxCatchments c;                  // the lists as uploaded (smashx_prcp_indices builds its own from them)
         int *d_list = nullptr, *d_begin = nullptr;
         float *d_state = nullptr, *d_mp = nullptr, *d_me = nullptr;
     } mf;
@@ -446,8 +444,7 @@ struct smashx_plan {
     struct PrcpIndices {
         int state = 0;                   // 0 = not built, 1 = ready for h_flwdst
         std::vector<float> h_flwdst;
-        std::vector<SxPiGauge> gauges;
-        long entries = 0, catchment_entries = 0;
+        SxPiHost h;                      // its list, dl and d2l live on the device only
         int* d_list = nullptr; float *d_dl = nullptr, *d_d2l = nullptr; SxPiGauge* d_gauges = nullptr;
         float *d_state = nullptr, *d_out = nullptr; int* d_flag = nullptr;
     } pi;
@@ -485,9 +482,10 @@ struct smashx_plan {
         double* d_sums = nullptr; size_t sums_cap = 0;
         int span = 0;
     } ann;
+    // ensemble path (smashx_multiple_run): tables built and buffers allocated on first use, all its own
     struct Ens {
         bool tables = false;
-        int nlevels = 0; std::vector<int> level_begin;
+        SxForest forest;
         int *d_up = nullptr, *d_upn = nullptr, *d_order = nullptr, *d_gauge_k = nullptr;
         float *base = nullptr, *plane = nullptr;
         float *sample = nullptr, *state = nullptr, *qt = nullptr, *qg = nullptr, *gj = nullptr, *cost = nullptr, *qout = nullptr;
@@ -495,8 +493,7 @@ struct smashx_plan {
         hipEvent_t ev_a = nullptr, ev_b = nullptr;
         int info[4] = {0, 0, 0, 0};      // batch size, time chunk, batches, chunks per batch of the last call
         float device_ms = 0.f;
-        // catchment-resident path (smashx_uniform_costs, sx_resident.h): host copies of the forest and the per-thread tables built from them
-        std::vector<int> h_up, h_upn, h_order, h_level;
+        // catchment-resident path (smashx_uniform_costs, sx_resident.h): the per-thread tables built from the forest
         int res_state = 0;               // 0 = not built, 1 = ready, 2 = refused (res_refusal says why)
         std::string res_refusal;
         int *r_cell = nullptr, *r_level = nullptr, *r_upline = nullptr, *r_upn = nullptr, *r_ownline = nullptr, *r_gfirst = nullptr, *r_gnext = nullptr;
@@ -992,9 +989,7 @@ int smashx_plan_create(const smashx_config* cfg, const smashx_mesh* mesh, smashx
     if (rc0 != 0) { std::string e = p->sch.error; delete p; return fail(rc0 == -5 ? SMASHX_E_MESH : SMASHX_E_ARG, e); }
     p->tiled = tiled;
     if (!tiled) {
-        p->h_flwdir.resize((size_t)cfg->nrow * cfg->ncol);
-        for (size_t c = 0; c < p->h_flwdir.size(); ++c) { const int d = mesh->flwdir[c]; p->h_flwdir[c] = (d >= 1 && d <= 8 && mesh->active_cell[c] == 1) ? (signed char)d : 0; }
-        p->h_flwdir_grid.resize(p->h_flwdir.size());
+        p->h_flwdir_grid.resize((size_t)cfg->nrow * cfg->ncol);
         for (size_t c = 0; c < p->h_flwdir_grid.size(); ++c) { const int d = mesh->flwdir[c]; p->h_flwdir_grid[c] = (d >= 1 && d <= 8) ? (signed char)d : 0; }
     }
     p->n = p->sch.n; p->npad = (p->n + SX_VBLOCK - 1) / SX_VBLOCK * SX_VBLOCK;
@@ -2675,46 +2670,20 @@ int smashx_forward(smashx_plan* p, smashx_parameters* params, const smashx_param
 // of res_cost / res_qsim.  The plan's own device state (uploaded fields, states, gauge series, timing) is not touched.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-const int ENS_DROW[8] = {-1, -1, 0, 1, 1, 1, 0, -1};      // D8 codes 1..8 = N, NE, E, SE, S, SW, W, NW (sx_plan.cpp)
-const int ENS_DCOL[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-
+// the forest (sx_tablehost.h) and what both sample paths hold on the device
 int ens_tables(smashx_plan* p) {
     auto& E = p->ens;
     if (E.tables) return 0;
-    const int n = p->n, nrow = p->cfg.nrow, ncol = p->cfg.ncol;
-    std::vector<int> up((size_t)n * 8, -1), upn(n, 0), parent(n, -1), level(n, 0), indeg(n, 0);
-    for (int k = 0; k < n; ++k) {
-        const int c = p->sch.cell_flat[k], row = c % nrow, col = c / nrow;
-        for (int i = 0; i < 8; ++i) {       // the neighbour at -D[i] drains into me iff its code == i + 1 (md_routing_operator.f90:29-31,45)
-            const int rn = row - ENS_DROW[i], cn = col - ENS_DCOL[i];
-            if (rn < 0 || rn >= nrow || cn < 0 || cn >= ncol) continue;
-            const long fn = rn + (long)cn * nrow;
-            const int ku = p->sch.k_of_flat[fn];
-            if (ku >= 0 && p->h_flwdir[fn] == i + 1) { up[(size_t)k * 8 + upn[k]++] = ku; parent[ku] = k; }
-        }
-        indeg[k] = upn[k];
-    }
-    std::vector<int> topo; topo.reserve(n);
-    for (int k = 0; k < n; ++k) if (indeg[k] == 0) topo.push_back(k);
-    for (size_t i = 0; i < topo.size(); ++i) {
-        const int k = topo[i], q = parent[k];
-        if (q >= 0) { level[q] = std::max(level[q], level[k] + 1); if (--indeg[q] == 0) topo.push_back(q); }
-    }
-    if ((int)topo.size() != n) return fail(SMASHX_E_MESH, "flow directions contain a cycle over active cells");
-    int nlev = 0;
-    for (int k = 0; k < n; ++k) nlev = std::max(nlev, level[k] + 1);
-    std::vector<int> order(n), begin(nlev + 1, 0);
-    for (int k = 0; k < n; ++k) begin[level[k] + 1]++;
-    for (int l = 0; l < nlev; ++l) begin[l + 1] += begin[l];
-    { std::vector<int> fill(begin.begin(), begin.end() - 1); for (int k = 0; k < n; ++k) order[fill[level[k]]++] = k; }
+    std::string cycle;
+    SxForest F = sx_forest(p->sch, p->h_flwdir_grid.data(), &cycle);
+    if (!cycle.empty()) return fail(SMASHX_E_MESH, cycle);
     int rc;
-    if ((rc = p->upload_vec(&E.d_up, up)) || (rc = p->upload_vec(&E.d_upn, upn)) || (rc = p->upload_vec(&E.d_order, order))) return rc;
+    if ((rc = p->upload_vec(&E.d_up, F.up)) || (rc = p->upload_vec(&E.d_upn, F.upn)) || (rc = p->upload_vec(&E.d_order, F.order))) return rc;
     if ((rc = p->upload_vec(&E.d_gauge_k, p->sch.gauge_k.empty() ? std::vector<int>(1, 0) : p->sch.gauge_k))) return rc;
     if ((rc = p->dmalloc(&E.base, (size_t)SX_NSLOTS * p->npad))) return rc;
     if ((rc = p->dmalloc(&E.plane, (size_t)p->n2))) return rc;
     HIPCHK(hipEventCreate(&E.ev_a)); HIPCHK(hipEventCreate(&E.ev_b));
-    E.nlevels = nlev; E.level_begin = begin; E.tables = true;
-    E.h_up = up; E.h_upn = upn; E.h_order = order; E.h_level = level;
+    E.forest = std::move(F); E.tables = true;
     return 0;
 }
 
@@ -2843,8 +2812,8 @@ int smashx_multiple_run(smashx_plan* p, const smashx_parameters* params, const s
             const int t0 = c * Tc, T = std::min(Tc, nt - t0);
             hipLaunchKernelGGL(vert[st - 1], gV, bV, 0, sV, p->A, E, t0, T);
             // one launch per level of the forest: stream order is the dependency
-            for (int l = 0; l < X.nlevels; ++l) {
-                const int i0 = X.level_begin[l], m = X.level_begin[l + 1] - i0;
+            for (int l = 0; l < X.forest.nlevels; ++l) {
+                const int i0 = X.forest.level_begin[l], m = X.forest.level_begin[l + 1] - i0;
                 for (int o = 0; o < m; o += 65535)
                     hipLaunchKernelGGL(sx_k_ens_route_fwd, dim3(SP / 64, std::min(65535, m - o)), b64, 0, sV, p->A, E, i0 + o, T);
             }
@@ -2876,28 +2845,6 @@ namespace {
 int res_tables(smashx_plan* p) {
     auto& X = p->ens;
     if (X.res_state) return 0;
-    const int n = p->n, ng = p->ng;
-    if (n > SX_RES_MAXCELLS) {
-        X.res_state = 2;
-        X.res_refusal = std::to_string(n) + " active cells, the resident kernel holds one cell per thread and at most " + std::to_string(SX_RES_MAXCELLS);
-        return 0;
-    }
-    std::vector<int> pos(n), parent(n, -1), own(n, -1), cell(n), level(n), upn(n), upline((size_t)n * 8, 0), gfirst(n, -1), gnext(std::max(ng, 1), -1);
-    for (int i = 0; i < n; ++i) pos[X.h_order[i]] = i;
-    for (int k = 0; k < n; ++k)
-        for (int c = 0; c < X.h_upn[k]; ++c) parent[X.h_up[(size_t)k * 8 + c]] = k;
-    size_t floats = 0;
-    for (int i = 0; i < n; ++i) {          // lines in thread order: neighbours in a level are neighbours in LDS
-        const int k = X.h_order[i];
-        cell[i] = k; level[i] = X.h_level[k]; upn[i] = X.h_upn[k];
-        if (parent[k] < 0) continue;
-        const int D = X.h_level[parent[k]] - X.h_level[k];     // >= 1
-        int lg = 1;
-        while ((1 << lg) < D + 1) ++lg;                          // D + 1 slots, rounded up to a power of two (sx_resident.h)
-        if (floats + ((size_t)1 << lg) > ((size_t)1 << 26)) { floats = (size_t)1 << 26; break; }
-        own[i] = (int)(floats << 5) | lg;
-        floats += (size_t)1 << lg;
-    }
     // what a workgroup may claim: the device's limit less what the kernel holds statically (the exact-libm build's tables)
     int lim = 0, dev = 0;
     HIPCHK(hipGetDevice(&dev));
@@ -2905,27 +2852,14 @@ int res_tables(smashx_plan* p) {
     hipFuncAttributes fa{};
     HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&sx_k_res_fwd<1>)));
     X.res_static = fa.sharedSizeBytes;
-    if (floats * 4 + X.res_static > (size_t)lim) {
-        X.res_state = 2;
-        X.res_refusal = "the delay lines of the catchment need " + (floats >= ((size_t)1 << 26) ? std::string("more than 268435456") : std::to_string(floats * 4 + X.res_static)) +
-                        " B of LDS, a workgroup may claim " + std::to_string(lim);
-        return 0;
-    }
-    for (int i = 0; i < n; ++i) {
-        const int k = cell[i];
-        for (int c = 0; c < upn[i]; ++c) upline[(size_t)i * 8 + c] = own[pos[X.h_up[(size_t)k * 8 + c]]];
-    }
-    for (int g = ng - 1; g >= 0; --g) {      // gauges of a cell chained in gauge order
-        const int k = p->sch.gauge_k[g];
-        if (k < 0 || k >= n) continue;
-        gnext[g] = gfirst[pos[k]]; gfirst[pos[k]] = g;
-    }
+    const SxResHost R = sx_res_host_tables(X.forest, p->sch.gauge_k, p->ng, (size_t)lim, X.res_static);
+    if (!R.refusal.empty()) { X.res_state = 2; X.res_refusal = R.refusal; return 0; }
     int rc;
-    if ((rc = p->upload_vec(&X.r_cell, cell)) || (rc = p->upload_vec(&X.r_level, level)) || (rc = p->upload_vec(&X.r_upline, upline)) ||
-        (rc = p->upload_vec(&X.r_upn, upn)) || (rc = p->upload_vec(&X.r_ownline, own)) || (rc = p->upload_vec(&X.r_gfirst, gfirst)) ||
-        (rc = p->upload_vec(&X.r_gnext, gnext))) return rc;
-    X.res_block = std::max(64, (n + 63) / 64 * 64);
-    X.res_lds = floats * 4;
+    if ((rc = p->upload_vec(&X.r_cell, R.cell)) || (rc = p->upload_vec(&X.r_level, R.level)) || (rc = p->upload_vec(&X.r_upline, R.upline)) ||
+        (rc = p->upload_vec(&X.r_upn, R.upn)) || (rc = p->upload_vec(&X.r_ownline, R.ownline)) || (rc = p->upload_vec(&X.r_gfirst, R.gfirst)) ||
+        (rc = p->upload_vec(&X.r_gnext, R.gnext))) return rc;
+    X.res_block = std::max(64, (p->n + 63) / 64 * 64);
+    X.res_lds = R.floats * 4;
     X.res_state = 1;
     return 0;
 }
@@ -2935,8 +2869,7 @@ int res_tables(smashx_plan* p) {
 int smashx_uniform_costs(smashx_plan* p, const smashx_parameters* params, const smashx_states* states, int nfields,
                          const int* ind, const float* sample, int nsamples, float* res_cost) {
     SampleBatches B;
-    int rc = B.open(p, "smashx_uniform_costs", "optimize_sbs", params, states, nfields, ind, sample, nsamples, res_cost, SX_RES_MAXCELLS,
-                    [](int n) { return std::to_string(n) + " active cells, the resident kernel holds one cell per thread and at most " + std::to_string(SX_RES_MAXCELLS); });
+    int rc = B.open(p, "smashx_uniform_costs", "optimize_sbs", params, states, nfields, ind, sample, nsamples, res_cost, SX_RES_MAXCELLS, sx_res_cells_refusal);
     if (rc || (rc = res_tables(p))) return rc;
     auto& X = p->ens;
     if (X.res_state == 2) return fail(SMASHX_E_UNSUPPORTED, "smashx_uniform_costs: " + X.res_refusal);
@@ -2944,7 +2877,7 @@ int smashx_uniform_costs(smashx_plan* p, const smashx_parameters* params, const 
     // samples per batch: one launch of as many workgroups as the batch has samples
     if ((rc = B.arrays(std::min((nsamples + 63) / 64 * 64, 16384), p->nt, &X.res_ms))) return rc;
     SxResTables R{};
-    R.nlevels = X.nlevels; R.cell = X.r_cell; R.level = X.r_level; R.upline = X.r_upline; R.upn = X.r_upn; R.ownline = X.r_ownline;
+    R.nlevels = X.forest.nlevels; R.cell = X.r_cell; R.level = X.r_level; R.upline = X.r_upline; R.upn = X.r_upn; R.ownline = X.r_ownline;
     R.gfirst = X.r_gfirst; R.gnext = X.r_gnext;
     static void (*const kernel[5])(SxDeviceArrays, SxEnsArrays, SxResTables, int) = {sx_k_res_fwd<1>, sx_k_res_fwd<2>, sx_k_res_fwd<3>,
                                                                                        sx_k_res_fwd<4>, sx_k_res_fwd<5>};
@@ -2960,7 +2893,7 @@ int smashx_uniform_costs(smashx_plan* p, const smashx_parameters* params, const 
         if ((rc = B.costs()) || (rc = B.end(out.data()))) return rc;
     }
     for (int i = 0; i < nsamples; ++i) res_cost[i] = out[i];      // only a complete call writes res_cost
-    X.res_info[0] = p->n; X.res_info[1] = X.nlevels; X.res_info[2] = X.res_block; X.res_info[3] = (int)(X.res_lds + X.res_static);
+    X.res_info[0] = p->n; X.res_info[1] = X.forest.nlevels; X.res_info[2] = X.res_block; X.res_info[3] = (int)(X.res_lds + X.res_static);
     return 0;
 }
 
@@ -3429,11 +3362,9 @@ int smashx_adjust_interception(smashx_plan* p, int nday, const int* day_index, f
 
 // ---------------------------------------------------------------------------------------------------------
 // compute_mean_forcing (mw_forcing_statistic.f90:18-75) on the resident forcing: kernel and mapping in sx_meanforcing.h.
-// mask_upstream_cells (mw_mask.f90:11-54) is restated here without recursion: from the gauge cell, every neighbour whose D8 code points
-// at a cell already taken is taken, over the whole grid; the mask read in flat order (row + col * nrow) IS the column-major order of
-// the reference's sum.  The lists are built on the first call and kept with the plan, each padded with -1 to whole blocks of 64
-// entries.  A launch covers SX_MF_PIECE entries of every list (SMASHX_MF_PIECE); the running sums live in a device buffer of the plan
-// between launches.
+// The catchment lists (sx_catchment_lists, sx_tablehost.h: mask_upstream_cells restated, column-major, padded to whole blocks of 64
+// entries) are built on the first call and kept with the plan.  A launch covers SX_MF_PIECE entries of every list (SMASHX_MF_PIECE);
+// the running sums live in a device buffer of the plan between launches.
 // ---------------------------------------------------------------------------------------------------------
 #define SX_MF_PIECE (1 << 20)
 namespace {
@@ -3441,45 +3372,12 @@ int mf_tables(smashx_plan* p) {
     auto& M = p->mf;
     if (M.state == 1) return 0;
     if (M.state == 2) return fail(SMASHX_E_UNSUPPORTED, M.refusal);
-    const int nrow = p->cfg.nrow, ncol = p->cfg.ncol, ng = p->ng;
-    const long n2 = p->n2;
-    std::vector<int> list; std::vector<char> mask((size_t)n2); std::vector<long> stack;
-    M.begin.assign(1, 0); M.count.clear();
-    for (int g = 0; g < ng; ++g) {
-        std::fill(mask.begin(), mask.end(), 0);
-        const long c0 = p->sch.cell_flat[p->sch.gauge_k[g]];
-        mask[c0] = 1; stack.assign(1, c0);
-        while (!stack.empty()) {
-            const long c = stack.back(); stack.pop_back();
-            const int row = (int)(c % nrow), col = (int)(c / nrow);
-            for (int i = 0; i < 8; ++i) {       // the neighbour at -D[i] drains into (row, col) iff its code is i + 1
-                const int rn = row - ENS_DROW[i], cn = col - ENS_DCOL[i];
-                if (rn < 0 || rn >= nrow || cn < 0 || cn >= ncol) continue;
-                const long fn = rn + (long)cn * nrow;
-                if (p->h_flwdir_grid[fn] == i + 1 && !mask[fn]) { mask[fn] = 1; stack.push_back(fn); }
-            }
-        }
-        for (long c = 0; c < n2; ++c) {
-            if (!mask[c]) continue;
-            const int k = p->sch.k_of_flat[c];
-            if (k < 0) {
-                M.state = 2;
-                M.refusal = "smashx_mean_forcing: the catchment of gauge " + std::to_string(g) + " contains the inactive cell (" + std::to_string(c % nrow) + ", " +
-                            std::to_string(c / nrow) + "): the plan holds no forcing there";
-                M.begin.clear();
-                return fail(SMASHX_E_UNSUPPORTED, M.refusal);
-            }
-            list.push_back(k);
-        }
-        M.count.push_back((int)list.size() - M.begin[g]);
-        while (list.size() % 64) list.push_back(-1);
-        if (list.size() > (size_t)INT_MAX - 64) return fail(SMASHX_E_UNSUPPORTED, "smashx_mean_forcing: the catchment lists of all gauges together exceed 2^31 entries");
-        M.begin.push_back((int)list.size());
-    }
+    const int ng = p->ng;
+    M.c = sx_catchment_lists(p->sch, p->h_flwdir_grid.data(), ng, &M.refusal);
+    if (!M.refusal.empty()) { M.state = 2; return fail(SMASHX_E_UNSUPPORTED, M.refusal); }
     int rc;
-    if ((rc = p->upload_vec(&M.d_list, list))) return rc;
-    if ((rc = p->upload_vec(&M.d_begin, M.begin))) return rc;
-    M.h_list = std::move(list);
+    if ((rc = p->upload_vec(&M.d_list, M.c.list))) return rc;
+    if ((rc = p->upload_vec(&M.d_begin, M.c.begin))) return rc;
     const size_t ntpad = (size_t)((p->nt + 63) / 64) * 64;
     if ((rc = p->dmalloc(&M.d_state, (size_t)4 * ng * ntpad))) return rc;
     if ((rc = p->dmalloc(&M.d_mp, (size_t)ng * p->nt))) return rc;
@@ -3500,7 +3398,7 @@ int smashx_mean_forcing(smashx_plan* p, float* mean_prcp, float* mean_pet) {
     if ((rc = close_forcing(p))) return rc;
     auto& M = p->mf;
     const int ng = p->ng, nt = p->nt;
-    const int longest = *std::max_element(M.count.begin(), M.count.end());
+    const int longest = *std::max_element(M.c.count.begin(), M.c.count.end());
     const int nbp = piece_entries("SMASHX_MF_PIECE", SX_MF_PIECE) / 64;
     hipStream_t sV = p->stream;
     const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_LW_WAVES);
@@ -3520,19 +3418,15 @@ int smashx_mean_forcing(smashx_plan* p, float* mean_prcp, float* mean_pet) {
     if (err != hipSuccess) return fail(SMASHX_E_HIP, std::string("smashx_mean_forcing: ") + hipGetErrorString(err));
     if (getenv("SMASHX_VERBOSE"))
         fprintf(stderr, "smashx: mean_forcing %d gauges x %d steps, longest catchment %d cells, %d list entries: %.3f ms on the device, %d launches\n", ng, nt, longest,
-                std::accumulate(M.count.begin(), M.count.end(), 0), device_ms(p), launches);
+                std::accumulate(M.c.count.begin(), M.c.count.end(), 0), device_ms(p), launches);
     return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // compute_prcp_indices (mw_forcing_statistic.f90:77-220) on the resident rain: kernel and mapping in sx_prcpindices.h.
-// Host side, per gauge, as the reference does it once per call: d = flwdst - flwdst(gauge) over the WHOLE grid in fp32; the catchment
-// (the list smashx_mean_forcing builds, column-major) with its d and d * d; flwdst_qtl = quantile1d_r (m_statistic.f90:231-277) of the
-// catchment's d at q = real(i) / 100, i = 0, 10 .. 100, every operation rounded on its own; wf, the cumulated counts of the
-// catchment's d per bin; the ten bins (qtl(k-1) < d <= qtl(k)) over the whole grid, column-major inside a bin; the cell
-// (gauge_row, gauge_row), which the reference reads for pwf(1) (:181 indexes the column with the gauge's row: reproduced as written).
-// Whatever the reference would read and the plan holds no forcing for is refused.  The tables are kept with the plan and rebuilt when
-// the caller's flwdst differs from the plane they were built for.  A launch covers SX_PI_PIECE list entries of every gauge
+// The host side (sx_pi_host_tables, sx_tablehost.h) does per gauge what the reference does once per call: the distances, their
+// quantiles and bin counts, the catchment and the ten distance bins as one padded list.  The tables are kept with the plan and rebuilt
+// when the caller's flwdst differs from the plane they were built for.  A launch covers SX_PI_PIECE list entries of every gauge
 // (SMASHX_PI_PIECE).
 // ---------------------------------------------------------------------------------------------------------
 #define SX_PI_PIECE (1 << 20)
@@ -3541,20 +3435,7 @@ void pi_drop(smashx_plan* p) {
     auto& Q = p->pi;
     p->dfree(Q.d_list); p->dfree(Q.d_dl); p->dfree(Q.d_d2l); p->dfree(Q.d_gauges);
     Q.d_list = nullptr; Q.d_dl = Q.d_d2l = nullptr; Q.d_gauges = nullptr;
-    Q.state = 0; Q.h_flwdst.clear(); Q.gauges.clear();
-}
-
-// quantile1d_r for the eleven quantiles; b sorted, n >= 2
-void pi_quantiles(const std::vector<float>& b, float* qtl) {
-    const int n = (int)b.size();
-    for (int i = 0; i < SX_PI_NQ; ++i) {
-        const float q = (float)(10 * i) / 100.f;
-        if (q >= 1.f) { qtl[i] = b[n - 1]; continue; }
-        const float div = q * (float)(n - 1) + 1.f;
-        const int qt = (int)floorf(div);
-        const float r = fmodf(div, (float)qt);
-        qtl[i] = (1.f - r) * b[qt - 1] + r * b[qt];
-    }
+    Q.state = 0; Q.h_flwdst.clear(); Q.h = SxPiHost();
 }
 
 int pi_tables(smashx_plan* p, const float* flwdst) {
@@ -3562,66 +3443,13 @@ int pi_tables(smashx_plan* p, const float* flwdst) {
     const long n2 = p->n2;
     if (Q.state == 1 && memcmp(Q.h_flwdst.data(), flwdst, (size_t)n2 * sizeof(float)) == 0) return 0;
     pi_drop(p);
-    const int nrow = p->cfg.nrow, ncol = p->cfg.ncol, ng = p->ng;
-    auto refuse = [&](const std::string& why) { return fail(SMASHX_E_UNSUPPORTED, "smashx_prcp_indices: " + why); };
-    std::vector<int> list; std::vector<float> dl, d2l, d((size_t)n2), b; std::vector<int> bins[SX_PI_NQ];
-    std::vector<SxPiGauge> G((size_t)ng);
-    long catchment = 0;
-    for (int g = 0; g < ng; ++g) {
-        SxPiGauge& Gg = G[g];
-        const long c0 = p->sch.cell_flat[p->sch.gauge_k[g]];
-        const int row = (int)(c0 % nrow);
-        const float f0 = flwdst[c0];
-        for (long c = 0; c < n2; ++c) d[c] = flwdst[c] - f0;
-        const int nc = M.count[g];
-        if (nc < 2) return refuse("the catchment of gauge " + std::to_string(g) + " has " + std::to_string(nc) + " cell: the reference's quantile reads two");
-        const int krr = row < ncol ? p->sch.k_of_flat[row + (long)row * nrow] : -1;
-        if (krr < 0)
-            return refuse("gauge " + std::to_string(g) + ": the reference reads the rain of the cell (gauge_row, gauge_row) = (" + std::to_string(row) + ", " +
-                          std::to_string(row) + "), which is " + (row < ncol ? "inactive: the plan holds no forcing there" : "outside the grid"));
-        Gg.krr = krr; Gg.lb = (int)list.size(); Gg.db = (int)dl.size();
-        b.clear();
-        for (int j = 0; j < nc; ++j) {
-            const int k = M.h_list[(size_t)M.begin[g] + j];
-            const float dc = d[p->sch.cell_flat[k]];
-            list.push_back(k); dl.push_back(dc); d2l.push_back(dc * dc); b.push_back(dc);
-        }
-        while (list.size() % 64) { list.push_back(-1); dl.push_back(0.f); d2l.push_back(0.f); }
-        catchment += nc;
-        Gg.sec[0] = 0; Gg.sec[1] = (int)((list.size() - (size_t)Gg.lb) / 64);
-        std::sort(b.begin(), b.end());
-        float qtl[SX_PI_NQ];
-        pi_quantiles(b, qtl);
-        Gg.wf[0] = 1.f; Gg.cnt[0] = 0.f;
-        for (int k = 1; k < SX_PI_NQ; ++k) {
-            int cnt = 0;
-            for (float v : b) cnt += (v > qtl[k - 1] && v <= qtl[k]) ? 1 : 0;
-            Gg.wf[k] = Gg.wf[k - 1] + (float)cnt;
-            bins[k].clear();
-        }
-        for (long c = 0; c < n2; ++c) {                        // flat order is the column-major order of the reference's sums
-            for (int k = 1; k < SX_PI_NQ; ++k) {
-                if (!(d[c] > qtl[k - 1] && d[c] <= qtl[k])) continue;
-                const int kk = p->sch.k_of_flat[c];
-                if (kk < 0)
-                    return refuse("the inactive cell (" + std::to_string(c % nrow) + ", " + std::to_string(c / nrow) + ") lies in distance bin " + std::to_string(k) +
-                                  " of gauge " + std::to_string(g) + ": the plan holds no forcing there");
-                bins[k].push_back(kk);
-            }
-        }
-        for (int k = 1; k < SX_PI_NQ; ++k) {
-            list.insert(list.end(), bins[k].begin(), bins[k].end());
-            while (list.size() % 64) list.push_back(-1);
-            Gg.cnt[k] = (float)bins[k].size();
-            Gg.sec[k + 1] = (int)((list.size() - (size_t)Gg.lb) / 64);
-        }
-        if (list.size() > (size_t)INT_MAX - 64) return refuse("the lists of all gauges together exceed 2^31 entries");
-    }
+    const int ng = p->ng;
+    std::string refusal;
+    SxPiHost T = sx_pi_host_tables(p->sch, M.c, flwdst, ng, &refusal);
+    if (!refusal.empty()) return fail(SMASHX_E_UNSUPPORTED, refusal);
     int rc;
-    if ((rc = p->upload_vec(&Q.d_list, list))) return rc;
-    if ((rc = p->upload_vec(&Q.d_dl, dl))) return rc;
-    if ((rc = p->upload_vec(&Q.d_d2l, d2l))) return rc;
-    if ((rc = p->upload_vec(&Q.d_gauges, G))) return rc;
+    if ((rc = p->upload_vec(&Q.d_list, T.list)) || (rc = p->upload_vec(&Q.d_dl, T.dl)) || (rc = p->upload_vec(&Q.d_d2l, T.d2l)) ||
+        (rc = p->upload_vec(&Q.d_gauges, T.gauges))) return rc;
     if (!Q.d_state) {
         const size_t ntpad = (size_t)((p->nt + 63) / 64) * 64;
         if ((rc = p->dmalloc(&Q.d_state, (size_t)SX_PI_NF * ng * ntpad))) return rc;
@@ -3629,7 +3457,8 @@ int pi_tables(smashx_plan* p, const float* flwdst) {
         if ((rc = p->dmalloc(&Q.d_flag, (size_t)ng * p->nt))) return rc;
     }
     Q.h_flwdst.assign(flwdst, flwdst + n2);
-    Q.gauges = std::move(G); Q.entries = (long)list.size(); Q.catchment_entries = catchment;
+    T.list = {}; T.dl = {}; T.d2l = {};
+    Q.h = std::move(T);
     Q.state = 1;
     return 0;
 }
@@ -3648,7 +3477,7 @@ int smashx_prcp_indices(smashx_plan* p, const float* flwdst, float* prcp_indices
     auto& Q = p->pi;
     const int ng = p->ng, nt = p->nt;
     int longest = 0;
-    for (int g = 0; g < ng; ++g) longest = std::max(longest, Q.gauges[g].sec[SX_PI_NQ]);
+    for (int g = 0; g < ng; ++g) longest = std::max(longest, Q.h.gauges[g].sec[SX_PI_NQ]);
     const int nbp = piece_entries("SMASHX_PI_PIECE", SX_PI_PIECE) / 64;
     hipStream_t sV = p->stream;
     const dim3 grid((unsigned)((nt + 63) / 64), (unsigned)ng), block(64 * SX_LW_WAVES);
@@ -3673,7 +3502,7 @@ int smashx_prcp_indices(smashx_plan* p, const float* flwdst, float* prcp_indices
     }
     if (getenv("SMASHX_VERBOSE"))
         fprintf(stderr, "smashx: prcp_indices %d gauges x %d steps, longest list %d blocks, %ld list entries (%ld of catchments), %ld pairs written: %.3f ms on the device, %d launches\n",
-                ng, nt, longest, Q.entries, Q.catchment_entries, written, device_ms(p), launches);
+                ng, nt, longest, Q.h.entries, Q.h.catchment_entries, written, device_ms(p), launches);
     return 0;
 }
 

@@ -7,14 +7,6 @@
 #include <map>
 #include <numeric>
 
-namespace {
-// D8: code k = 1..8 = N, NE, E, SE, S, SW, W, NW flows to (row + DROW[k-1], col + DCOL[k-1])
-// (reference smash/mesh/mw_meshing.f90:163-164); the solver's upstream test
-// (md_routing_operator.f90:29-31,45) is the mirror image: neighbour i drains into me iff its code == i.
-const int DROW[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
-const int DCOL[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-}  // namespace
-
 int sx_build_schedule(int nrow, int ncol, const int* flwdir, const int* active_cell, int ng, const int* gauge_pos,
                       int group_size, const int* rect, SxSchedule& s, const int* own, int sublevels) {
     const int M = group_size;
@@ -44,13 +36,12 @@ int sx_build_schedule(int nrow, int ncol, const int* flwdir, const int* active_c
         code[a] = fd;
         if (part)
             for (int i = 0; i < 8; ++i) {   // neighbour at -D[i] drains into me iff its code == i+1
-                const int rn = row - DROW[i], cn = col - DCOL[i];
-                if (rn < 0 || rn >= nrow || cn < 0 || cn >= ncol || inside(rn, cn)) continue;
-                const long fn = rn + (long)cn * nrow;
+                const long fn = sx_d8_upstream(nrow, ncol, row, col, i);
+                if (fn < 0 || inside((int)(fn % nrow), (int)(fn / nrow))) continue;
                 if (active_cell[fn] == 1 && flwdir[fn] == i + 1) { rflat.push_back((int)fn); rparent.push_back(a); }
             }
         if (fd < 1 || fd > 8) continue;
-        const int r2 = row + DROW[fd - 1], c2 = col + DCOL[fd - 1];
+        const int r2 = row + SX_DROW[fd - 1], c2 = col + SX_DCOL[fd - 1];
         if (r2 < 0 || r2 >= nrow || c2 < 0 || c2 >= ncol) continue;
         const long f2 = r2 + (long)c2 * nrow;
         if (active_cell[f2] != 1) continue;            // receiver inactive: catchment outlet

@@ -13,6 +13,17 @@
 #include <string>
 #include <vector>
 
+// D8: code k = 1..8 = N, NE, E, SE, S, SW, W, NW flows to (row + SX_DROW[k-1], col + SX_DCOL[k-1])
+// (reference smash/mesh/mw_meshing.f90:163-164); the solver's upstream test (md_routing_operator.f90:29-31,45, mw_mask.f90:29-31) is
+// the mirror image: the neighbour at -D[i] drains into me iff its code == i + 1.
+inline constexpr int SX_DROW[8] = {-1, -1, 0, 1, 1, 1, 0, -1};
+inline constexpr int SX_DCOL[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+// flat index (row + col * nrow) of the neighbour of (row, col) at -D[i], i = 0..7, or -1 off the grid
+inline long sx_d8_upstream(int nrow, int ncol, int row, int col, int i) {
+    const int rn = row - SX_DROW[i], cn = col - SX_DCOL[i];
+    return (rn < 0 || rn >= nrow || cn < 0 || cn >= ncol) ? -1 : rn + (long)cn * nrow;
+}
+
 struct SxSchedule {
     int nrow = 0, ncol = 0;
     int n = 0;                       // active cells

@@ -1,6 +1,6 @@
 // sx_prcpindices.h -- mw_forcing_statistic::compute_prcp_indices (smash/solver/routine/mw_forcing_statistic.f90:77-220) on the rain the
 // plan holds in HBM: per gauge g and time step t, with d = flwdst - flwdst(gauge) (host side, with its quantiles flwdst_qtl and the
-// cumulated bin counts wf: smashx.hip),
+// cumulated bin counts wf: sx_tablehost.h),
 //     mask   = upstream(g) and rain >= 0;  n = count(mask);  minv_n = 1 / real(n)
 //     sum_p, sum_p2, sum_d, sum_d2, sum_pd, sum_pd2 = sums over mask of m, m*m, d, d*d, m*d, (m*d)*d
 //     sum_b(k) = sum of the rain over { flwdst_qtl(k-1) < d <= flwdst_qtl(k) } of the WHOLE grid, gap values as they are, k = 2 .. 11
@@ -21,18 +21,9 @@
 #pragma once
 
 #include "sx_listwalk.h"
+#include "sx_tables.h"                      // SX_PI_NQ, SxPiGauge
 
-#define SX_PI_NQ 11                         // quantiles 0, 0.1 .. 1
 #define SX_PI_NF 18                         // state fields: count, six sums, the open bin sum, ten finished bin sums
-
-struct SxPiGauge {
-    int lb;                                 // first entry of the gauge in the list (a multiple of 64)
-    int db;                                 // first entry of its catchment in the distance arrays (a multiple of 64)
-    int sec[SX_PI_NQ + 1];                  // section s is blocks [sec[s], sec[s + 1]) of the gauge
-    float wf[SX_PI_NQ];
-    float cnt[SX_PI_NQ];                    // cnt[k], k = 1 .. 10: real(count(mask_k)); cnt[0] unused
-    int krr;                                // plan cell of (gauge_row, gauge_row)
-};
 
 __device__ __forceinline__ float sx_pi_uniform(float v, int j) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j)); }
 

@@ -3,7 +3,7 @@
 // where both the loop of forwards and the ensemble are launch latency on an empty card.  Here ONE workgroup holds the whole catchment
 // of one sample, one thread per active cell, and ONE launch marches the whole period: reservoir levels and hlr never leave registers.
 //
-// Threads are ordered by level of the forest (the order / level tables of ens_tables) and time is skewed by level: at super-step u
+// Threads are ordered by level of the forest (the order / level tables of sx_forest, sx_tablehost.h) and time is skewed by level: at super-step u
 // the cell of level l does its step t = u - l, if 0 <= t < nt.  Every upstream cell of a cell lies in a lower level, so its discharge
 // of step t was written at an earlier super-step (t + l_up < t + l_down): one __syncthreads() per super-step is the dependency,
 // nt + nlevels - 1 super-steps in all.  No flags, no spinning, no atomics; every thread of the block reaches every barrier, idle
@@ -24,12 +24,11 @@
 #pragma once
 
 #include "sx_ensemble.h"
-
-#define SX_RES_MAXCELLS 1024      // one cell per thread, one workgroup per sample
+#include "sx_tables.h"            // SX_RES_MAXCELLS
 
 struct SxResTables {
     int nlevels;
-    const int* cell;       // [n] plan cell of thread i (cells by level: ens_tables' order)
+    const int* cell;       // [n] plan cell of thread i (cells by level: sx_forest's order)
     const int* level;      // [n] its level
     const int* upline;     // [n][8] delay line of every upstream cell in D8 order: (first float << 5) | log2(slots); the first upn entries
     const int* upn;        // [n] by thread
