@@ -79,7 +79,8 @@ def test_forward_vs_reference_golden(name):
         e = gu.rel_l2(out.qsim[i], g.fwd["qsim"][i])
         assert e <= gu.tol(g.noise["qsim"][i]), (i, e, g.noise["qsim"][i])
     assert abs(out.cost - g.fwd["cost"]) <= gu.tol_cost(g.noise["cost"], g.fwd["cost"]), (out.cost, g.fwd["cost"])
-    assert abs(out.cost_jreg - g.fwd["cost_jreg"]) <= 1e-6 * abs(g.fwd["cost_jreg"]), (out.cost_jreg, g.fwd["cost_jreg"])
+    # the regulariser is summed in the reference's order and passes through no libm: equal in both builds (sx_jreg.h)
+    assert np.float32(out.cost_jreg).tobytes() == np.float32(g.fwd["cost_jreg"]).tobytes(), (out.cost_jreg, g.fwd["cost_jreg"])
     for k in gu.STRUCT_STATES[g.structure]:
         e = gu.rel_l2(getattr(out.fstates, k), g.fwd["fstates"][k])
         assert e <= gu.tol_fstate(k, g.noise["fstates"][k]), (k, e, g.noise["fstates"][k])
