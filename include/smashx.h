@@ -174,6 +174,11 @@ typedef struct {
 } smashx_forcing_layout;
 int smashx_set_forcing_layout(smashx_plan* plan, const smashx_forcing_layout* layout);
 int smashx_forcing_info(const smashx_plan* plan, int* compact, double* bytes_per_cellstep);
+/* Observations and options.  A gauge with a non-zero wgauge and no qobs >= 0 on the steps optimize_start_step .. nt counts exactly as
+ * if its wgauge were 0: no cost, no place in the median, no seed (the compiled reference reads an unassigned local
+ * there).  The rule is applied by whichever of the two calls completes the pair, and again when either changes.  On a plan with
+ * median slots (smashx_set_median_slots) such a gauge that holds a slot is refused with SMASHX_E_UNSUPPORTED by that same call,
+ * which then leaves the plan as it was: dropping it would change the slot count of the whole decomposition. */
 int smashx_set_qobs(smashx_plan* plan, const float* qobs /* (ng,nt) */);
 int smashx_set_options(smashx_plan* plan, const smashx_options* opt);
 
@@ -302,7 +307,8 @@ int smashx_set_halo(smashx_plan* plan, float* d_out_buf, float* d_in_buf, smashx
  *    Between the two phases of the cost kernel the nslots values are summed over the ranks: by ncclAllReduce on the routing stream
  *    when smashx_set_exchange is active, else by reduce_fn (host: sums n floats in place over the tiles; called once per sweep by
  *    every tile).  Each rank's cost_jobs then carries its own gauges' share of the median (the interpolation weights of its slots),
- *    so the sum over ranks is the reference's jobs.  nslots = 0 switches it off.  Call before smashx_set_options. */
+ *    so the sum over ranks is the reference's jobs.  nslots = 0 switches it off.  Call before smashx_set_options; called after
+ *    options and qobs are set, it refuses (SMASHX_E_UNSUPPORTED) a slot given to a negative-weight gauge without data, as they do. */
 typedef int (*smashx_reduce_fn)(void* user, float* values, int n);
 int smashx_set_median_slots(smashx_plan* plan, int nslots, const int* slot_of_gauge, smashx_reduce_fn reduce_fn, void* user);
 

@@ -435,10 +435,28 @@ static float median_b(int n, const float* dat, float* dat_b, float res_b) {
 /* mwd_cost.f90:37-156 (compute_jobs); with qsim_b != NULL also forward_db.f90:2553-2715 (compute_jobs_b).
  * Gauges with a negative weight enter a median instead of the weighted sum; as soon as there is one, the
  * median REPLACES the weighted sum (mwd_cost.f90:139-154) and jobs_b no longer reaches the weighted gauges. */
+/* The weights compute_jobs works with: a gauge with no qo >= 0 on the steps optimize_start_step .. nt counts exactly as if its weight
+ * were 0 (no cost, no place in the median, no seed).  The one deliberate departure from the compiled reference, whose j_imd is an
+ * unassigned local there.  Caller frees. */
+float* orc_effective_wgauge(const orc_config* cfg, const int* flwacc, const int* gauge_pos, const float* qobs, const float* wgauge) {
+    const int ng = cfg->ng, nt = cfg->nt, s0 = cfg->optimize_start_step - 1;
+    float* we = (float*)malloc(sizeof(float) * (size_t)(ng > 0 ? ng : 1));
+    for (int g = 0; g < ng; ++g) {
+        int row = gauge_pos[g], col = gauge_pos[g + ng], any = 0;
+        for (int t = s0; t < nt && !any; ++t) {
+            float qo = qobs[g + (long)ng * t] * cfg->dt / ((float)flwacc[row + (long)col * cfg->nrow] * cfg->dx * cfg->dx) * 1e3f;
+            if (qo >= 0.f) any = 1;
+        }
+        we[g] = any ? wgauge[g] : 0.f;
+    }
+    return we;
+}
+
 static int compute_jobs(const orc_config* cfg, const int* flwacc, const int* gauge_pos, const float* area,
-                        const float* qobs, const float* wgauge, const float* qsim, float* jobs, float jobs_b,
+                        const float* qobs, const float* wgauge_in, const float* qsim, float* jobs, float jobs_b,
                         float* qsim_b) {
     const int ng = cfg->ng, nt = cfg->nt, s0 = cfg->optimize_start_step - 1, n = nt - s0;
+    float* wgauge = orc_effective_wgauge(cfg, flwacc, gauge_pos, qobs, wgauge_in);
     float* qo = (float*)malloc(sizeof(float) * (size_t)(n > 0 ? n : 1));
     float* qs = (float*)malloc(sizeof(float) * (size_t)(n > 0 ? n : 1));
     float* qs_b = (float*)malloc(sizeof(float) * (size_t)(n > 0 ? n : 1));
@@ -450,25 +468,21 @@ static int compute_jobs(const orc_config* cfg, const int* flwacc, const int* gau
     for (int g = 0; g < ng; ++g) {
         if (!(wgauge[g] > 0.f || wgauge[g] < 0.f)) continue;
         int row = gauge_pos[g], col = gauge_pos[g + ng];
-        int any = 0;
         for (int i = 0; i < n; ++i) {
             qs[i] = qsim[g + (long)ng * (s0 + i)] * cfg->dt / area[g] * 1e3f;
             qo[i] = qobs[g + (long)ng * (s0 + i)] * cfg->dt /
                     ((float)flwacc[row + (long)col * cfg->nrow] * cfg->dx * cfg->dx) * 1e3f;
-            if (qo[i] >= 0.f) any = 1;
         }
         float gauge_jobs = 0.f, j_imd = 0.f;
-        for (int j = 0; j < cfg->njf; ++j) {
-            if (any) {
-                switch (cfg->jobs_fun[j]) {
-                    case ORC_NSE: j_imd = nse(qo, qs, n); break;
-                    case ORC_KGE: j_imd = kge(qo, qs, n); break;
-                    case ORC_KGE2: { float imd = kge(qo, qs, n); j_imd = imd * imd; } break;
-                    case ORC_SE: j_imd = se(qo, qs, n); break;
-                    case ORC_RMSE: j_imd = rmse(qo, qs, n); break;
-                    case ORC_LOGARITHMIC: j_imd = logarithmic(qo, qs, n); break;
-                    default: break;
-                }
+        for (int j = 0; j < cfg->njf; ++j) {   /* any(qo >= 0) holds: a gauge without data has weight 0 above */
+            switch (cfg->jobs_fun[j]) {
+                case ORC_NSE: j_imd = nse(qo, qs, n); break;
+                case ORC_KGE: j_imd = kge(qo, qs, n); break;
+                case ORC_KGE2: { float imd = kge(qo, qs, n); j_imd = imd * imd; } break;
+                case ORC_SE: j_imd = se(qo, qs, n); break;
+                case ORC_RMSE: j_imd = rmse(qo, qs, n); break;
+                case ORC_LOGARITHMIC: j_imd = logarithmic(qo, qs, n); break;
+                default: break;
             }
             gauge_jobs = gauge_jobs + cfg->wjobs_fun[j] * j_imd;
         }
@@ -484,12 +498,10 @@ static int compute_jobs(const orc_config* cfg, const int* flwacc, const int* gau
         for (int g = ng - 1; g >= 0; --g) {
             if (!(wgauge[g] > 0.f || wgauge[g] < 0.f)) continue;
             int row = gauge_pos[g], col = gauge_pos[g + ng];
-            int any = 0;
             for (int i = 0; i < n; ++i) {
                 qs[i] = qsim[g + (long)ng * (s0 + i)] * cfg->dt / area[g] * 1e3f;
                 qo[i] = qobs[g + (long)ng * (s0 + i)] * cfg->dt /
                         ((float)flwacc[row + (long)col * cfg->nrow] * cfg->dx * cfg->dx) * 1e3f;
-                if (qo[i] >= 0.f) any = 1;
                 qs_b[i] = 0.f;
             }
             float gauge_jobs_b;
@@ -497,7 +509,6 @@ static int compute_jobs(const orc_config* cfg, const int* flwacc, const int* gau
             else gauge_jobs_b = arr_b[--arr_size];
             for (int j = cfg->njf - 1; j >= 0; --j) {
                 j_imd_b = j_imd_b + cfg->wjobs_fun[j] * gauge_jobs_b;
-                if (!any) continue; /* control 8: j_imd_b keeps accumulating (forward_db.f90:2672-2704) */
                 switch (cfg->jobs_fun[j]) {
                     case ORC_NSE: nse_b(qo, qs, qs_b, n, j_imd_b); j_imd_b = 0.f; break;
                     case ORC_KGE: kge_b(qo, qs, qs_b, n, j_imd_b); j_imd_b = 0.f; break;
@@ -512,7 +523,7 @@ static int compute_jobs(const orc_config* cfg, const int* flwacc, const int* gau
                 qsim_b[g + (long)ng * (s0 + i)] = qsim_b[g + (long)ng * (s0 + i)] + cfg->dt * 1e3f * qs_b[i] / area[g];
         }
     }
-    free(qo); free(qs); free(qs_b); free(arr); free(arr_b);
+    free(qo); free(qs); free(qs_b); free(arr); free(arr_b); free(wgauge);
     return 0;
 }
 

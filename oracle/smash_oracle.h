@@ -90,6 +90,10 @@ void orc_census(long long* counts /* ORC_CEN_N */);
  * (smash_oracle.c).  Only tests/test_bounds_cpu.py sets it, to compare base_forward where a NaN reaches gr_transfer's floor. */
 void orc_set_reference_max(int on);
 
+/* The weights the cost of every entry below works with: wgauge, with 0 for a gauge that has no qobs >= 0 on the steps
+ * optimize_start_step .. nt (smash_oracle.c).  malloc'ed; the caller frees. */
+float* orc_effective_wgauge(const orc_config* cfg, const int* flwacc, const int* gauge_pos, const float* qobs, const float* wgauge);
+
 int orc_forward(const orc_config* cfg, const int* flwdir, const int* flwacc, const int* path,
                 const int* active_cell, const int* gauge_pos, const float* area, const float* prcp,
                 const float* pet, const float* qobs, const float* wgauge, float* params,

@@ -437,8 +437,9 @@ static void heap_sort2(int n, float* arr, float* arr_d) {   /* HEAP_SORT_D: the 
 }
 
 static void jobs_d(const orc_config* cfg, const int* flwacc, const int* gauge_pos, const float* area, const float* qobs,
-                   const float* wgauge, const float* qsim, const float* qsim_d, float* jobs_out, float* jobs_d_out) {
+                   const float* wgauge_in, const float* qsim, const float* qsim_d, float* jobs_out, float* jobs_d_out) {
     const int ng = cfg->ng, nt = cfg->nt, s0 = cfg->optimize_start_step - 1, n = nt - s0;
+    float* wgauge = orc_effective_wgauge(cfg, flwacc, gauge_pos, qobs, wgauge_in);   /* a gauge without data counts as weight 0 */
     const size_t m = (size_t)(n > 0 ? n : 1);
     /* sizeof(float), not 4: liboracle64.so compiles these statements with float = double */
     float* qo = (float*)malloc(sizeof(float) * m); float* qs = (float*)malloc(sizeof(float) * m); float* qsd = (float*)malloc(sizeof(float) * m);
@@ -447,25 +448,22 @@ static void jobs_d(const orc_config* cfg, const int* flwacc, const int* gauge_po
     float jobs = 0.f, jd = 0.f;
     for (int g = 0; g < ng; ++g) {
         if (!(wgauge[g] > 0.f || wgauge[g] < 0.f)) continue;
-        int row = gauge_pos[g], col = gauge_pos[g + ng], any = 0;
+        int row = gauge_pos[g], col = gauge_pos[g + ng];
         for (int i = 0; i < n; ++i) {
             qs[i] = qsim[g + (long)ng * (s0 + i)] * cfg->dt / area[g] * 1e3f;
             qsd[i] = 1e3f * cfg->dt * qsim_d[g + (long)ng * (s0 + i)] / area[g];
             qo[i] = qobs[g + (long)ng * (s0 + i)] * cfg->dt / ((float)flwacc[row + (long)col * cfg->nrow] * cfg->dx * cfg->dx) * 1e3f;
-            if (qo[i] >= 0.f) any = 1;
         }
         float gj = 0.f, gj_d = 0.f, j_imd = 0.f, j_imd_d = 0.f;
-        for (int j = 0; j < cfg->njf; ++j) {
-            if (any) {
-                switch (cfg->jobs_fun[j]) {
-                    case ORC_NSE: j_imd_d = nse_d(qo, qs, qsd, n, &j_imd); break;
-                    case ORC_KGE: j_imd_d = kge_d(qo, qs, qsd, n, &j_imd); break;
-                    case ORC_KGE2: { float imd, imd_d = kge_d(qo, qs, qsd, n, &imd); j_imd_d = 2.f * imd * imd_d; j_imd = imd * imd; } break;
-                    case ORC_SE: j_imd_d = se_d(qo, qs, qsd, n, &j_imd); break;
-                    case ORC_RMSE: j_imd_d = rmse_d(qo, qs, qsd, n, &j_imd); break;
-                    case ORC_LOGARITHMIC: j_imd_d = logarithmic_d(qo, qs, qsd, n, &j_imd); break;
-                    default: break;
-                }
+        for (int j = 0; j < cfg->njf; ++j) {   /* any(qo >= 0) holds for every gauge that still has a weight */
+            switch (cfg->jobs_fun[j]) {
+                case ORC_NSE: j_imd_d = nse_d(qo, qs, qsd, n, &j_imd); break;
+                case ORC_KGE: j_imd_d = kge_d(qo, qs, qsd, n, &j_imd); break;
+                case ORC_KGE2: { float imd, imd_d = kge_d(qo, qs, qsd, n, &imd); j_imd_d = 2.f * imd * imd_d; j_imd = imd * imd; } break;
+                case ORC_SE: j_imd_d = se_d(qo, qs, qsd, n, &j_imd); break;
+                case ORC_RMSE: j_imd_d = rmse_d(qo, qs, qsd, n, &j_imd); break;
+                case ORC_LOGARITHMIC: j_imd_d = logarithmic_d(qo, qs, qsd, n, &j_imd); break;
+                default: break;
             }
             gj_d = gj_d + cfg->wjobs_fun[j] * j_imd_d;
             gj = gj + cfg->wjobs_fun[j] * j_imd;
@@ -489,7 +487,7 @@ static void jobs_d(const orc_config* cfg, const int* flwacc, const int* gauge_po
         }
     }
     *jobs_out = jobs; *jobs_d_out = jd;
-    free(qo); free(qs); free(qsd); free(arr); free(arr_d);
+    free(qo); free(qs); free(qsd); free(arr); free(arr_d); free(wgauge);
 }
 
 static void bounds(const int* active, int nrow, int ncol, int row, int col, int* mnc, int* mxc, int* mnr, int* mxr) {

@@ -328,7 +328,8 @@ struct smashx_plan {
     bool have_forcing = false, have_options = false, have_qobs = false, uploaded = false;
     bool chunk_ready = false, adj_ready = false;
     smashx_options opt{};
-    std::vector<float> wgauge;
+    std::vector<float> wgauge;       // the caller's weights; d_wgauge holds the effective ones (effective_wgauge)
+    std::vector<int> gauge_flwacc_h;
     hipStream_t stream = nullptr;    // vertical kernels, uploads/downloads ("V stream")
     hipStream_t stream_r = nullptr;  // routing + cost kernels ("R stream"); overlaps the V stream chunk by chunk
     int Tp = 0;                      // pipeline sub-chunk length inside a storage chunk
@@ -1152,6 +1153,7 @@ int smashx_plan_create(const smashx_config* cfg, const smashx_mesh* mesh, smashx
     TRY(p->dmalloc(&A.qg, (size_t)std::max(p->ngc, 1) * p->nt));
     TRY(p->upload_vec(&p->d_gauge_gid, p->gauge_gid.empty() ? std::vector<int>(1, 0) : p->gauge_gid));
     TRY(p->upload_vec(&p->d_gauge_flwacc, gfl));
+    p->gauge_flwacc_h = gfl;
     std::vector<float> area(std::max(p->ng, 1), 1.f);
     for (int g = 0; g < p->ng; ++g) area[g] = mesh->area[g];
     TRY(p->upload_vec(&p->d_area, area));
@@ -1380,12 +1382,44 @@ int smashx_set_forcing_device_block(smashx_plan* p, int t0, int t1, const float*
     return 0;
 }
 
+namespace {
+// The weights the cost stage reads (d_wgauge): the caller's, with 0 for a gauge that has no qo >= 0 on the steps optimize_start_step ..
+// nt.  Such a gauge counts exactly as if its weight were 0: no cost, no place in the median, no seed.  qo is formed
+// as prepare_signature and sx_qo form it.  On a plan with median slots an empty gauge that holds a slot is refused: dropping it would
+// change the slot count of the whole decomposition.  Nothing of the plan is changed.
+bool gauge_has_data(const smashx_plan* p, const std::vector<float>& h_qobs, int g, int s0) {
+    for (int t = s0; t < p->nt; ++t) {
+        const float qo = h_qobs[(size_t)g * p->nt + t] * p->cfg.dt / ((float)p->gauge_flwacc_h[g] * p->cfg.dx * p->cfg.dx) * 1e3f;
+        if (qo >= 0.f) return true;
+    }
+    return false;
+}
+// (smashx_set_median_slots is meant to come before the options; called after options and qobs it makes the same refusal itself)
+int effective_wgauge(const smashx_plan* p, const std::vector<float>& w, const std::vector<float>& h_qobs, int s0, std::vector<float>& eff) {
+    eff = w;
+    for (int g = 0; g < p->ng; ++g) {
+        if (!(w[g] > 0.f || w[g] < 0.f)) continue;
+        if (gauge_has_data(p, h_qobs, g, s0)) continue;
+        if (p->med_nslots > 0 && w[g] < 0.f && p->med_slot_h[g] >= 0)
+            return fail(SMASHX_E_UNSUPPORTED, "gauge " + std::to_string(g + 1) + " holds a median slot and has no qobs >= 0 from optimize_start_step on: "
+                        "it would leave the median; declare the slots without it (smashx_set_median_slots) and give it wgauge = 0");
+        eff[g] = 0.f;
+    }
+    return 0;
+}
+}  // namespace
+
 int smashx_set_qobs(smashx_plan* p, const float* qobs) {
     if (!p || (!qobs && p->ng > 0)) return fail(SMASHX_E_ARG, "null argument");
     int rc = set_device(p); if (rc) return rc;
     std::vector<float> tr((size_t)std::max(p->ng, 1) * p->nt);
     for (int g = 0; g < p->ng; ++g)
         for (int t = 0; t < p->nt; ++t) tr[(size_t)g * p->nt + t] = qobs[g + (size_t)p->ng * t];   // (ng,nt) column-major -> [g][t]
+    if (!p->have_qobs || tr != p->h_qobs) {      // (the same observations again leave the effective weights as they are)
+        std::vector<float> eff;
+        if ((rc = effective_wgauge(p, p->wgauge, tr, p->opt.optimize_start_step - 1, eff))) return rc;
+        HIPCHK(hipMemcpy(p->d_wgauge, eff.data(), eff.size() * 4, hipMemcpyHostToDevice));
+    }
     HIPCHK(hipMemcpy(p->d_qobs, tr.data(), tr.size() * 4, hipMemcpyHostToDevice));
     p->have_qobs = true;
     if (tr != p->h_qobs) {          // (the drop-ins hand the same observations over before every call: nothing of the criteria's is redone then)
@@ -1607,10 +1641,12 @@ int smashx_set_options(smashx_plan* p, const smashx_options* o) {
     for (int j = 0; j < o->njr; ++j)
         if (o->jreg_fun[j] < SMASHX_PRIOR || o->jreg_fun[j] > SMASHX_HARD_SMOOTHING)
             return fail(SMASHX_E_UNSUPPORTED, "unknown jreg_fun (prior / smoothing / hard_smoothing, mwd_cost.f90:199-224)");
-    {   // the signature criteria first: a refusal leaves the plan's options as they were, without the criteria's tables (run_cost checks)
+    std::vector<float> eff;
+    {   // the signature criteria and the gauges without data first: a refusal leaves the plan's options as they were, without the criteria's tables (run_cost checks)
         std::vector<float> w(std::max(p->ng, 1), 0.f);
         for (int g = 0; g < p->ng; ++g) w[g] = o->wgauge ? o->wgauge[g] : 1.f / p->ng;
         if ((rc = prepare_signature(p, o, w))) return rc;
+        if (p->have_qobs && (rc = effective_wgauge(p, w, p->h_qobs, o->optimize_start_step - 1, eff))) return rc;
     }
     p->opt = *o;
     p->jr_ready = false;
@@ -1623,7 +1659,8 @@ int smashx_set_options(smashx_plan* p, const smashx_options* o) {
             return fail(SMASHX_E_ARG, "smashx_set_median_slots and wgauge disagree: exactly the negative-weight gauges have a slot");
         p->wgauge[g] = w;
     }
-    HIPCHK(hipMemcpy(p->d_wgauge, p->wgauge.data(), p->wgauge.size() * 4, hipMemcpyHostToDevice));
+    if (!p->have_qobs) eff = p->wgauge;
+    HIPCHK(hipMemcpy(p->d_wgauge, eff.data(), eff.size() * 4, hipMemcpyHostToDevice));
     p->have_options = true;
     p->hyp.options = true;
     return 0;
@@ -2296,6 +2333,11 @@ int smashx_set_median_slots(smashx_plan* p, int nslots, const int* slot_of_gauge
         sl[g] = slot_of_gauge[g];
         if (sl[g] < -1 || sl[g] >= nslots) return fail(SMASHX_E_ARG, "slot_of_gauge out of range");
     }
+    if (p->have_qobs)      // after options and qobs: a slot for a negative-weight gauge without data is refused here as it is there
+        for (int g = 0; g < p->ng; ++g) {
+            if (!(p->wgauge[g] < 0.f) || sl[g] < 0 || gauge_has_data(p, p->h_qobs, g, p->opt.optimize_start_step - 1)) continue;
+            return fail(SMASHX_E_UNSUPPORTED, "gauge " + std::to_string(g + 1) + " is given a median slot and has no qobs >= 0 from optimize_start_step on");
+        }
     if (p->d_med_slot) { p->dfree(p->d_med_slot); p->dfree(p->d_medx); p->dfree(p->d_medx_idx); }
     if ((rc = p->upload_vec(&p->d_med_slot, sl))) return rc;
     p->med_slot_h = sl;

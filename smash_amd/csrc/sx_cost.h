@@ -209,7 +209,8 @@ __device__ inline void sx_heap_sort_idx(int n, float* arr, int* idx) {
 }
 
 // the per-criterion adjoint coefficients of one gauge given the seed of its gauge_jobs (COMPUTE_JOBS_B, forward_db.f90:2656-2704);
-// j_imd_b is the reference's scalar, carried from gauge to gauge
+// j_imd_b is the reference's scalar.  It is 0 again after every criterion of a gauge with data, and a gauge without data never gets
+// here: the host gives it weight 0 (effective_wgauge, smashx.hip), so nothing is carried from gauge to gauge
 __device__ inline void sx_cost_gauge_coef(const SxCostArgs& C, int g, float gauge_jobs_b, float& j_imd_b) {
     const SxGaugeSums S = C.sums[g];
     const bool any = S.n > 0;
@@ -309,7 +310,7 @@ __global__ void sx_k_cost_final(SxCostArgs C, int adjoint, int phase = 0) {
     }
     C.out[0] = jobs;
     if (!adjoint) return;
-    float j_imd_b = 0.f;   // carried across gauges exactly like the reference's scalar (forward_db.f90:2656-2704)
+    float j_imd_b = 0.f;   // the reference's scalar (forward_db.f90:2656-2704); 0 between gauges, see sx_cost_gauge_coef
     for (int g = C.ng - 1; g >= 0; --g) {
         for (int j = 0; j < SX_MAXJF; ++j) { SxCostCoef z; z.kind = 0; z.c_xy = z.c_yy = z.c_y = z.c = 0.f; z.i0 = z.i1 = -1; C.coef[g * SX_MAXJF + j] = z; }
         const float w = C.wgauge[g];
